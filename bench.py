@@ -1,6 +1,6 @@
 """Benchmark of the Lloyd-iteration hot path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
 
 A "step" is one Lloyd iteration of ``KMeans.fit`` (assign -> partial stats ->
@@ -10,8 +10,13 @@ enqueued in batches with one host synchronisation per batch, as ``fit`` runs
 them (``LloydRunner.run``).  Default workload
 = the metric's configuration, N=100M rows, d=64, k=256 (fits one MI355X: 25.6
 GB); the N rows are split over the ranks (strong scaling).  Rank 0 prints one
-JSON line with ``roofline`` (dominant kernel, HIP-event timed on its stream)
-and ``cpu_baseline`` (the oracle's per-point restatement of the reference
+JSON line.  A plain run sets up, warms up, times the K steps and prints the
+rate (``value``, ``ms_per_step``); ``--dump-outputs DIR`` also writes what the
+last timed step computed as ``DIR/<name>.npy`` (same inputs every run, so two
+builds compare output for output).  ``--full`` adds ``roofline`` and
+``kernel_avg_ms`` (HIP events around the dominant kernel inside the timed
+region, the other phases in two untimed steps), ``first_iter`` and
+``cpu_baseline`` (the oracle's per-point restatement of the reference
 closures, timed on this host on a bounded sample, N=1 only).
 """
 from __future__ import annotations
@@ -55,7 +60,14 @@ def parse():
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure what the headline figure does not need: per-kernel "
+                        "HIP-event times and the roofline, the first iterations after new centroids, the CPU "
+                        "baseline (a plain run sets up, warms up, times the steps and prints the line)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (centroids, cluster sizes, max shift, SSE when "
+                        "on, a seeded sample of the labels) as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     p.add_argument("--screen", type=int, default=-1, choices=[-1, 0, 1, 2, 3, 4, 5],
                    help="fused-path screen (km_set_screen): -1 the runtime's choice (4 = k_s1 where the "
                         "geometry has it), 0/1 fp16x3 k_fused16 with full statistics every iteration "
@@ -67,7 +79,8 @@ def parse():
                    help="after the fit steps, time P predict passes (km_predict, labels left in HBM; "
                         "kmeans_spark.py:321-352) and add a 'predict' object to the line")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline work per worker")
-    p.add_argument("--no-first-iter", action="store_true", help="skip the first-iterations timing (first_iter)")
+    p.add_argument("--no-first-iter", action="store_true",
+                   help="with --full: skip the first-iterations timing (first_iter)")
     p.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "traffic.json"),
                    help="per-launch HBM bytes from a rocprofv3 --pmc pass (optional)")
     return p.parse_args()
@@ -159,7 +172,14 @@ def main():
     N, d, k, centers = CONFIGS[args.config]
     sse = bool(args.sse) if args.sse is not None else args.config in SSE_CONFIGS
     comm = Communicator()
-    km = kmeans_amd.KMeans(k=k, max_iter=10 ** 9, tolerance=1e-300, seed=42, compute_sse=sse)
+
+    class BenchKMeans(kmeans_amd.KMeans):
+        def _empty_seed(self):
+            # the empty-cluster repair's seed, int(time.time()) in a fit (kmeans_spark.py:196): pinned here, so
+            # that every run of one command line has the same inputs and --dump-outputs compares build to build
+            return 20240607
+
+    km = BenchKMeans(k=k, max_iter=10 ** 9, tolerance=1e-300, seed=42, compute_sse=sse)
     km.verbose = False
     data = kmeans_amd.DeviceBlobs(n=N, d=d, n_centers=centers, box=10.0, std=1.0, seed=2024)
     run = km._make_runner(data, comm)
@@ -182,14 +202,15 @@ def main():
     eng.sync()
     comm.barrier()
     torch.cuda.synchronize()
-    # events only around the dominant kernel inside the timed region (each
+    # --full: events only around the dominant kernel inside the timed region (each
     # record costs a few us of stream time); the other phases' durations come
     # from two untimed steps after it
     # (one launch in 4 on the sub-millisecond steps of c1/c2, where each timed
     # launch's ~6 us of stream time would be 4% of the step)
-    eng.profile(True, phases=("assign", "stats"), every=4 if args.config in ("c1", "c2") else 1)
+    if args.full:
+        eng.profile(True, phases=("assign", "stats"), every=4 if args.config in ("c1", "c2") else 1)
     ran0 = run.iterations_ran
-    if world > 1:
+    if world > 1 and args.full:
         run.host_ms = {}   # host wall time per call kind (LloydRunner.run): where a multi-rank step goes
     t0 = time.perf_counter()
     run.run(km, log, args.warmup + args.steps, first=args.warmup)
@@ -202,6 +223,90 @@ def main():
     # early only on convergence (max_shift < 1e-300, i.e. an exact fixed
     # point), empties or NaN; the rate counts what ran, never args.steps
     ran = run.iterations_ran - ran0
+    dt = float(comm.allreduce_np(np.array([t1 - t0])).max()) if world == 1 else None
+    if world > 1:
+        import torch.distributed as dist
+        t = torch.tensor([t1 - t0], dtype=torch.float64,
+                         device=f"cuda:{torch.cuda.current_device()}" if dist.get_backend() == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, run, sse)
+    info = eng.info()
+    screen = eng.screen() if info["path"] == 2 else None
+
+    # everything below the timed region that the headline figure does not need
+    # runs only with --full (and the predict leg only with --predict)
+    roof = kernel_ms = first_iter = None
+    if args.full:
+        roof, kernel_ms = kernel_report(args, world, eng, run, km, log, info, screen, N, d, k)
+    pred = predict_leg(args, comm, eng, info, screen, d) if args.predict > 0 else None
+    if args.full and not args.no_first_iter:
+        first_iter = first_iterations(comm, eng, run, km, log, C0)
+    if rank == 0:
+        it_s = ran / dt
+        out = {
+            "metric": METRIC, "value": it_s, "unit": "Lloyd it/s", "n_gpus": world, "steps": args.steps,
+            "steps_ran": ran, "warmup": args.warmup, "ms_per_step": dt / max(ran, 1) * 1e3,
+            "higher_is_better": True,
+            "scaling": "strong", "vs_baseline": None, "dtype": "f32",
+            "data": "synthetic Gaussian blobs generated in HBM (centers U(-10,10), std 1)",
+            "config": {"workload": f"{args.config}: N={N} d={d} k={k}" + (", compute_sse=True" if sse else ""),
+                       "N": N, "d": d, "k": k, "compute_sse": sse,
+                       "parallelism": f"dp{world} (rows sharded, one RCCL all-reduce of k*(d+1) f64 per step)"},
+            "points_per_sec": N * it_s,
+            "resolve": {"q_rerank": run.last["q_rerank"], "q_full": run.last["q_full"]} if run.last else None,
+            "empty_repairs_on_device": run.device_repairs,
+            "screen": screen,
+            "predict": pred,
+            "arith": ("fp16 MFMA screen (balanced image, pairwise bound)" if screen in (2, 3) else
+                      "one fp16 MFMA per product, candidates re-scored in fp32 with a rigorous bound" +
+                      (", float64 delta statistics" if info["fused_stats"] else "") if screen == 4 else
+                      "one fp16 MFMA per product with a rigorous one-part bound" if screen == 5 else
+                      "fp16x3 MFMA screen with a rigorous bound") +
+                     ", float64 exact re-rank of ambiguous points, float64 partial sums",
+        }
+        if args.full:
+            out.update({
+                "roofline": roof, "kernel_avg_ms": kernel_ms, "first_iter": first_iter,
+                "host_ms_per_step": ({kk: v / max(ran, 1) for kk, v in host_ms.items()} if host_ms else None),
+                "cpu_baseline": (cpu_baseline(d, k, N, args.cpu_seconds)
+                                 if world == 1 and not args.no_cpu_baseline else None)})
+        print(json.dumps(out), flush=True)
+    if world > 1:
+        import torch.distributed as dist
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+DUMP_LABELS = 1 << 20   # labels written by --dump-outputs (a seeded sample of the rows when there are more)
+
+
+def dump_outputs(path, eng, run, sse):
+    """What the last timed step computed, as a caller of ``fit`` would get it
+    at that iteration: the committed centroids, the cluster sizes and largest
+    centroid shift of its update (and the SSE when on), and the labels of its
+    assignment pass -- all of them up to DUMP_LABELS rows, a seeded sample
+    (the same rows every run) beyond.  float64, labels float32 (k < 2^24)."""
+    os.makedirs(path, exist_ok=True)
+    last = run.last
+    arrays = {"centroids": eng.get_centroids(0),
+              "cluster_sizes": np.asarray(last["counts"], dtype=np.float64),
+              "max_shift": np.array([last["max_shift"]], dtype=np.float64)}
+    if sse:
+        arrays["sse"] = np.array([last["sse"]], dtype=np.float64)
+    labels = eng.labels()
+    if len(labels) > DUMP_LABELS:
+        labels = labels[np.sort(np.random.default_rng(2024).integers(0, len(labels), DUMP_LABELS))]
+    arrays["labels"] = labels.astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def kernel_report(args, world, eng, run, km, log, info, screen, N, d, k):
+    """--full: (roofline, kernel_avg_ms) from the HIP events recorded around
+    the dominant kernel in the timed region and around the other phases in two
+    untimed steps after it."""
     eng.profile(True, phases=("resolve", "update", "prep"), every=1)
     if world > 1:
         eng.time_collectives(True)   # HIP events around each all-reduce, engine stream
@@ -210,17 +315,8 @@ def main():
     eng.profile(False)
     coll = eng.collective_ms() if world > 1 else None
     eng.time_collectives(False)
-    dt = float(comm.allreduce_np(np.array([t1 - t0])).max()) if world == 1 else None
-    if world > 1:
-        import torch.distributed as dist
-        t = torch.tensor([t1 - t0], dtype=torch.float64,
-                         device=f"cuda:{torch.cuda.current_device()}" if dist.get_backend() == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        dt = float(t.item())
 
     kern = {name: eng.prof_read(name) for name in ("assign", "resolve", "stats", "update", "prep")}
-    info = eng.info()
-    screen = eng.screen() if info["path"] == 2 else None
     n_local = info["n"]
     flops_launch = 2.0 * n_local * k * d                 # algorithmic distance contraction
     bytes_stats = n_local * (d * 4 + 4)                  # X once + labels
@@ -322,85 +418,57 @@ def main():
         kernel_ms.pop("update")
     if coll is not None:
         kernel_ms["allreduce"] = coll[0] / max(coll[1], 1)
-    pred = None
-    if args.predict > 0:
-        # predict (kmeans_spark.py:321-352): one assignment pass with no
-        # statistics; labels stay in HBM (the LabelsRDD the caller collects)
-        eng.profile(True, phases=("assign", "resolve"), every=1)
-        eng.predict_device()                    # one untimed pass
-        eng.prof_read("assign"), eng.prof_read("resolve")
-        comm.barrier()
-        tp0 = time.perf_counter()
-        for _ in range(args.predict):
-            eng.predict_device()                # synchronises per pass
-        tp1 = time.perf_counter()
-        pa, pr = eng.prof_read("assign"), eng.prof_read("resolve")
-        eng.profile(False)
-        ms_a = pa[0] / max(pa[1], 1)
-        ms_w = (tp1 - tp0) / args.predict * 1e3
-        pred = {"passes": args.predict, "ms_per_pass": ms_w, "kernel_ms": {"assign": ms_a, "resolve": pr[0] / max(pr[1], 1)},
-                "gb_s": n_local * d * 4 / (ms_a / 1e3) / 1e9, "points_per_sec": n_local / (ms_w / 1e3),
-                "kernel": ("k_assign_small (labels only)" if info["path"] == 1 else
-                           "k_s1 (labels only)" if screen == 4 else
-                           "k_fused16 / k_fused (no statistics)" if info["fused_stats"] else
-                           "k_assign_wide" if info["dp"] > 256 else
-                           "k_assign_mfma16" if info["dp"] % 32 == 0 else "k_assign_mfma"),
-                "note": "ms_per_pass: host wall time per km_predict (launch + sync, labels left in HBM); "
-                        "gb_s: rows read once (N*d*4) / HIP-event time of the assign launch"}
+    return roof, kernel_ms
 
+
+def predict_leg(args, comm, eng, info, screen, d):
+    """--predict P: the 'predict' object of the line."""
+    n_local = info["n"]
+    # predict (kmeans_spark.py:321-352): one assignment pass with no
+    # statistics; labels stay in HBM (the LabelsRDD the caller collects)
+    eng.profile(True, phases=("assign", "resolve"), every=1)
+    eng.predict_device()                    # one untimed pass
+    eng.prof_read("assign"), eng.prof_read("resolve")
+    comm.barrier()
+    tp0 = time.perf_counter()
+    for _ in range(args.predict):
+        eng.predict_device()                # synchronises per pass
+    tp1 = time.perf_counter()
+    pa, pr = eng.prof_read("assign"), eng.prof_read("resolve")
+    eng.profile(False)
+    ms_a = pa[0] / max(pa[1], 1)
+    ms_w = (tp1 - tp0) / args.predict * 1e3
+    return {"passes": args.predict, "ms_per_pass": ms_w, "kernel_ms": {"assign": ms_a, "resolve": pr[0] / max(pr[1], 1)},
+            "gb_s": n_local * d * 4 / (ms_a / 1e3) / 1e9, "points_per_sec": n_local / (ms_w / 1e3),
+            "kernel": ("k_assign_small (labels only)" if info["path"] == 1 else
+                       "k_s1 (labels only)" if screen == 4 else
+                       "k_fused16 / k_fused (no statistics)" if info["fused_stats"] else
+                       "k_assign_wide" if info["dp"] > 256 else
+                       "k_assign_mfma16" if info["dp"] % 32 == 0 else "k_assign_mfma"),
+            "note": "ms_per_pass: host wall time per km_predict (launch + sync, labels left in HBM); "
+                    "gb_s: rows read once (N*d*4) / HIP-event time of the assign launch"}
+
+
+def first_iterations(comm, eng, run, km, log, C0):
+    """--full: the 'first_iter' object of the line."""
     # the iterations after new centroids (kmeans_spark.py:266-318 from the
     # start of a fit): the first runs the full-statistics screen (and, on the
     # k_s1 geometries, colours the chains), the second is the first delta
     # pass; steady state (ms_per_step) excludes both.  Host wall time of each
     # with its own sync, after the same set_centroids a fit makes
-    first_iter = None
-    if not args.no_first_iter:
-        eng.set_centroids(C0)
-        first_iter = {}
-        for i in range(2):
-            comm.barrier()
-            tf0 = time.perf_counter()
-            run.run(km, log, i + 1, first=i)
-            eng.sync()
-            tf1 = time.perf_counter()
-            first_iter[f"iter{i + 1}_ms"] = (tf1 - tf0) * 1e3
-        first_iter["note"] = ("host wall time per iteration with a sync, after set_centroids(C0): iter1 = full "
-                              "statistics pass (first screen after new centroids), iter2 = the first pass of the "
-                              "steady-state path (k_s1 with delta statistics on the c3 class)")
-    if rank == 0:
-        it_s = ran / dt
-        out = {
-            "metric": METRIC, "value": it_s, "unit": "Lloyd it/s", "n_gpus": world, "steps": args.steps,
-            "steps_ran": ran, "warmup": args.warmup, "ms_per_step": dt / max(ran, 1) * 1e3,
-            "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic Gaussian blobs generated in HBM (centers U(-10,10), std 1)",
-            "config": {"workload": f"{args.config}: N={N} d={d} k={k}" + (", compute_sse=True" if sse else ""),
-                       "N": N, "d": d, "k": k, "compute_sse": sse,
-                       "parallelism": f"dp{world} (rows sharded, one RCCL all-reduce of k*(d+1) f64 per step)"},
-            "points_per_sec": N * it_s, "roofline": roof, "kernel_avg_ms": kernel_ms,
-            "resolve": {"q_rerank": run.last["q_rerank"], "q_full": run.last["q_full"]} if run.last else None,
-            "empty_repairs_on_device": run.device_repairs,
-            "screen": screen,
-            "first_iter": first_iter,
-            "host_ms_per_step": ({kk: v / max(ran, 1) for kk, v in host_ms.items()} if host_ms else None),
-            "predict": pred,
-            "arith": ("fp16 MFMA screen (balanced image, pairwise bound)" if screen in (2, 3) else
-                      "one fp16 MFMA per product, candidates re-scored in fp32 with a rigorous bound" +
-                      (", float64 delta statistics" if info["fused_stats"] else "") if screen == 4 else
-                      "one fp16 MFMA per product with a rigorous one-part bound" if screen == 5 else
-                      "fp16x3 MFMA screen with a rigorous bound") +
-                     ", float64 exact re-rank of ambiguous points, float64 partial sums",
-        }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(d, k, N, args.cpu_seconds)
-        else:
-            out["cpu_baseline"] = None
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        import torch.distributed as dist
-        dist.barrier()
-        dist.destroy_process_group()
+    eng.set_centroids(C0)
+    first_iter = {}
+    for i in range(2):
+        comm.barrier()
+        tf0 = time.perf_counter()
+        run.run(km, log, i + 1, first=i)
+        eng.sync()
+        tf1 = time.perf_counter()
+        first_iter[f"iter{i + 1}_ms"] = (tf1 - tf0) * 1e3
+    first_iter["note"] = ("host wall time per iteration with a sync, after set_centroids(C0): iter1 = full "
+                          "statistics pass (first screen after new centroids), iter2 = the first pass of the "
+                          "steady-state path (k_s1 with delta statistics on the c3 class)")
+    return first_iter
 
 
 if __name__ == "__main__":

@@ -15,7 +15,7 @@ for CFG in ${CFGS:-c3}; do
   for R in $(seq ${ROUNDS:-2}); do
     for A in ${ARMS:-libkmeans_amd.so}; do
       N=${A%.so}
-      KM_LIB=$PWD/$P/$A timeout -k 10 400 python -u bench.py --config $CFG --steps ${STEPS:-20} --warmup ${WARMUP:-3} \
+      KM_LIB=$PWD/$P/$A timeout -k 10 400 python -u bench.py --full --config $CFG --steps ${STEPS:-20} --warmup ${WARMUP:-3} \
         --no-cpu-baseline $EXTRA > $OUT/$CFG.$N.$R.json 2> $OUT/$CFG.$N.$R.err || { echo "$CFG $A failed"; tail -5 $OUT/$CFG.$N.$R.err; exit 1; }
       python3 -c "import json;d=json.load(open('$OUT/$CFG.$N.$R.json'));print('$CFG $N $R', round(d['value'],3), round(d['ms_per_step'],3), {k:round(v,3) for k,v in d['kernel_avg_ms'].items()}, d['resolve'])"
     done

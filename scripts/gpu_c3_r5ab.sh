@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/r6_c3_r5ab; mkdir -p $OUT
 for R in 1 2; do
   (cd gpurun_ab_r5 && timeout -k 10 300 python -u bench.py --config c3 --no-cpu-baseline > ../$OUT/r5.$R.json 2> ../$OUT/r5.$R.err) || { echo r5 failed; tail -5 $OUT/r5.$R.err; exit 1; }
-  timeout -k 10 300 python -u bench.py --config c3 --no-cpu-baseline --no-first-iter > $OUT/r6.$R.json 2> $OUT/r6.$R.err || { echo r6 failed; tail -5 $OUT/r6.$R.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --config c3 --no-cpu-baseline --no-first-iter > $OUT/r6.$R.json 2> $OUT/r6.$R.err || { echo r6 failed; tail -5 $OUT/r6.$R.err; exit 1; }
   python3 -c "
 import json
 for t in ['r5','r6']:

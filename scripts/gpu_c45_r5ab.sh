@@ -8,7 +8,7 @@ OUT=gpurun_out/r6_c45_r5ab; mkdir -p $OUT
 for spec in c5:1 c5:2 c4:1; do
   C=${spec%%:*}; R=${spec##*:}
   (cd gpurun_ab_r5 && timeout -k 10 400 python -u bench.py --config $C --steps 10 --no-cpu-baseline > ../$OUT/$C.r5.$R.json 2> ../$OUT/$C.r5.$R.err) || { echo r5 $C failed; tail -5 $OUT/$C.r5.$R.err; exit 1; }
-  timeout -k 10 400 python -u bench.py --config $C --steps 10 --no-cpu-baseline --no-first-iter > $OUT/$C.r6.$R.json 2> $OUT/$C.r6.$R.err || { echo r6 $C failed; tail -5 $OUT/$C.r6.$R.err; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --config $C --steps 10 --no-cpu-baseline --no-first-iter > $OUT/$C.r6.$R.json 2> $OUT/$C.r6.$R.err || { echo r6 $C failed; tail -5 $OUT/$C.r6.$R.err; exit 1; }
   python3 -c "
 import json
 for t in ['r5','r6']:

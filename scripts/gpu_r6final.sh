@@ -19,11 +19,11 @@ tests)
   tail -2 $OUT/smoke.log
   ;;
 benches)
-  timeout -k 10 500 python -u bench.py --config c3 > $OUT/bench_c3.json 2> $OUT/bench_c3.err || { echo bench c3 failed; tail -20 $OUT/bench_c3.err; exit 1; }
+  timeout -k 10 500 python -u bench.py --full --config c3 > $OUT/bench_c3.json 2> $OUT/bench_c3.err || { echo bench c3 failed; tail -20 $OUT/bench_c3.err; exit 1; }
   python3 -c "import json;d=json.load(open('$OUT/bench_c3.json'));print('c3', round(d['value'],2), round(d['ms_per_step'],3), d['kernel_avg_ms'], d['first_iter'], d['cpu_baseline']['value'])"
   SPECS="c2| c4| c5|--predict,3 c5_poor|--predict,3 c3_shard8|" TAG=$TAG bash scripts/gpu_benches.sh || exit 1
   for CFG in c3 c4 c5; do
-    timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$CFG -o run -- python3 bench.py --config $CFG --no-cpu-baseline --no-first-iter > $OUT/trace_bench_$CFG.json 2> $OUT/trace_$CFG.err || { echo trace $CFG failed; tail -5 $OUT/trace_$CFG.err; exit 1; }
+    timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$CFG -o run -- python3 bench.py --full --config $CFG --no-cpu-baseline --no-first-iter > $OUT/trace_bench_$CFG.json 2> $OUT/trace_$CFG.err || { echo trace $CFG failed; tail -5 $OUT/trace_$CFG.err; exit 1; }
     python3 scripts/trace_summary.py $(ls $OUT/trace_$CFG/*kernel_trace.csv | head -1) > $OUT/trace_summary_$CFG.txt && head -6 $OUT/trace_summary_$CFG.txt
   done
   ;;

@@ -12,8 +12,8 @@ if [ -z "${SKIP_TESTS:-}" ]; then
   tail -1 $OUT/smoke.log
 fi
 for CFG in ${CFGS:-c3}; do
-  timeout -k 10 500 python -u bench.py --config $CFG ${BENCH_ARGS:-} > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err || { echo bench $CFG failed; tail -20 $OUT/bench_$CFG.err; exit 1; }
+  timeout -k 10 500 python -u bench.py --full --config $CFG ${BENCH_ARGS:-} > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err || { echo bench $CFG failed; tail -20 $OUT/bench_$CFG.err; exit 1; }
   cat $OUT/bench_$CFG.json
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$CFG -o run -- python3 bench.py --config $CFG --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/trace_bench_$CFG.json 2> $OUT/trace_$CFG.err || { echo trace $CFG failed; tail -5 $OUT/trace_$CFG.err; exit 1; }
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$CFG -o run -- python3 bench.py --full --config $CFG --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/trace_bench_$CFG.json 2> $OUT/trace_$CFG.err || { echo trace $CFG failed; tail -5 $OUT/trace_$CFG.err; exit 1; }
   python3 scripts/trace_summary.py $(ls $OUT/trace_$CFG/*kernel_trace.csv | head -1) > $OUT/trace_summary_$CFG.txt && head -8 $OUT/trace_summary_$CFG.txt
 done

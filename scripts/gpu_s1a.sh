@@ -8,7 +8,7 @@ rc=$?
 echo "pytest rc=$rc"; grep -E "PASS|FAIL|ERROR|passed|failed" $OUT/tests.log | tail -40
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 for CFG in ${CFGS:-c3}; do
-  timeout -k 10 300 python -u bench.py --config $CFG --steps ${STEPS:-20} --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err
+  timeout -k 10 300 python -u bench.py --full --config $CFG --steps ${STEPS:-20} --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err
   rc=$?; echo "bench $CFG rc=$rc"; cat $OUT/bench_$CFG.json; tail -3 $OUT/bench_$CFG.err
   if [ $rc -ne 0 ]; then exit $rc; fi
 done

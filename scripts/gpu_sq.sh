@@ -14,6 +14,6 @@ echo "$SQARMS" | tr ';' '\n' | while IFS='|' read -r name lib kn envs; do
   [ -z "$name" ] && continue
   mkdir -p $OUT/$name
   ( export KM_LIB=$PWD/$P/$lib; for e in $envs; do export "$e"; done
-    timeout -s KILL 240 rocprofv3 --pmc $CTRS --output-format csv -d $OUT/$name/pmc_sq -o run -- python3 bench.py --config ${CFG:-c3} --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline > $OUT/$name/log 2>&1 ) || { echo "$name failed"; tail -5 $OUT/$name/log; exit 1; }
+    timeout -s KILL 240 rocprofv3 --pmc $CTRS --output-format csv -d $OUT/$name/pmc_sq -o run -- python3 bench.py --full --config ${CFG:-c3} --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline > $OUT/$name/log 2>&1 ) || { echo "$name failed"; tail -5 $OUT/$name/log; exit 1; }
   python3 scripts/sq_summary.py $OUT/$name $OUT/$name.json "$kn" ${CFG:-c3} | python3 -c "import json,sys; d=json.load(sys.stdin); print('$name', {k: round(v,3) for k,v in d.items()})" || exit 1
 done

@@ -41,7 +41,7 @@ db[cfg] = {
     "algorithmic_bytes_per_launch": alg,
     "correction": "FETCH_SIZE (KB) x1024 x2: gfx950 reports half the bytes of wide streaming reads "
                   "(MI355X_MICROARCH.md, HBM); WRITE_SIZE x1024",
-    "source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes, python3 bench.py --config {cfg} "
+    "source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes, python3 bench.py --full --config {cfg} "
               "--steps 3 --warmup 1 --no-cpu-baseline (1 x MI355X)",
 }
 if os.environ.get("ROUND"):

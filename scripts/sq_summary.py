@@ -51,7 +51,7 @@ rows = [r for r in rows if r["duration_ms"] >= 0.01 * longest]
 mean = {k: sum(r[k] for r in rows) / len(rows) for k in rows[0] if k not in ("dispatch", "raw")}
 ctrs = sorted(rows[0]["raw"]) if rows else []
 json.dump({"kernel": f"{kname} ({cfg})",
-           "source": f"rocprofv3 --pmc {' '.join(ctrs)} -- python3 bench.py --config {cfg} --warmup 1 "
+           "source": f"rocprofv3 --pmc {' '.join(ctrs)} -- python3 bench.py --full --config {cfg} --warmup 1 "
                      "--no-cpu-baseline (scripts/gpu_sq.sh)",
            "notes": "clock = GRBM_GUI_ACTIVE/8 XCDs / dispatch duration; MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES / "
                     "1024 SIMDs / per-XCD GRBM cycles; SQ_* fractions of SQ_WAVE_CYCLES (quad-cycle units cancel)",
