@@ -54,6 +54,7 @@
 #include <float.h>
 
 #include "km_internal.h"
+#include "km_s1_ring.h"
 
 namespace km {
 
@@ -356,6 +357,10 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
   if (*A.gate) return;  // a stopped batch (km_update_async): the rest of it is a no-op
   constexpr int S1_WAVES = s1_waves(NS2, NB);
   constexpr int S1_RING = s1_ring(NS2, NB);
+  // a tile's 16 rows fill the ring at most twice (km_s1_ring.h: the slot
+  // arithmetic is checked exhaustively for both ring sizes at compile time)
+  static_assert(S1_RING == 12 || S1_RING == 16, "ring sizes covered by s1_ring_check");
+  static_assert(16 <= 2 * S1_RING && S1_TILE_ROWS == 16, "a tile may complete at most two batches");
   constexpr int DP = 32 * NS2;
   constexpr int FQ = 8 * NS2;  // features per quarter lane
   constexpr int KP = 32 * NB;
@@ -580,7 +585,7 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
     }
   };
   // the first nb rows of the wave's ring, one per quad: re-scored, emitted
-  uint32_t rc = 0;  // rows in the ring (< S1_RING between tiles)
+  uint32_t rc = 0;  // rows in the ring (< S1_RING between tiles: s1_ring_slot's rc)
   auto rescore = [&](uint32_t nb) {
     if constexpr (BATCH) {
       const bool act = (uint32_t)c16 < nb;
@@ -732,12 +737,41 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
           hp[0] = make_float4(hk[0][0], hk[0][1], hk[0][2], hk[0][3]);
           hp[1] = make_float4(hk[1][0], hk[1][1], hk[1][2], hk[1][3]);
         };
-        if (needy && rk < space) stash(rc + rk);
+        // a tile that leaves room: its rows go behind the rows carried in
+        // (batch 0 of s1_ring_slot, km_s1_ring.h: slot rc + rk).  A tile that
+        // fills the ring: the row's batch and slot from s1_ring_slot; each full
+        // batch is re-scored before the next one's rows take its slots.  A
+        // 12-slot ring can be filled twice by one tile (rc = 8, nn = 16), hence
+        // a loop, after which rc is below S1_RING again (`full` is
+        // wave-uniform: rc and nn are).
+        // Codegen (profiles/r7_s1_ring_regs.txt, r7_s1_ring_ab.json): ONE
+        // rescore site -- a second one in this lambda stops the compiler
+        // inlining rescore (a call with 400+ B of scratch per lane, the bench
+        // lines at half speed).  Batch 0 is stashed ahead of the branch, the
+        // previous kernel's form, which keeps the c3 line's time; the SSE
+        // instances, at the 168-register limit on the c4 geometry, spill one
+        // register in that form and stash batch 0 from inside the loop
+        constexpr bool EARLY0 = !SSE;
+        if (EARLY0 && needy && rk < space) stash(rc + rk);
         if (nn >= space) {
-          rescore((uint32_t)S1_RING);
-          if (needy && rk >= space) stash(rk - space);
-          rc = nn - space;
+          const S1RingSlot rs = s1_ring_slot((uint32_t)S1_RING, rc, nn, rk);
+          const uint32_t full = s1_ring_batch((uint32_t)S1_RING, rc + nn);  // batches this tile completes (>= 1)
+          if constexpr (EARLY0) {
+            for (uint32_t b = 1u;; ++b) {
+              rescore((uint32_t)S1_RING);
+              if (needy && rs.batch == b) stash(rs.slot);
+              if (b == full) break;
+            }
+          } else {
+            for (uint32_t b = 0u;; ++b) {
+              if (needy && rs.batch == b) stash(rs.slot);
+              if (b == full) break;
+              rescore((uint32_t)S1_RING);
+            }
+          }
+          rc = rs.rc;
         } else {
+          if (!EARLY0 && needy) stash(rc + rk);
           rc += nn;
         }
       }

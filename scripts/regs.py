@@ -25,4 +25,4 @@ for l in err.splitlines():
 for f, v in out.items():
     if pat in f:
         print(f"{f[:60]:60s} vgpr {v.get('VGPRs'):>4} agpr {v.get('AGPRs'):>4} spill {v.get('VGPRs Spill'):>3} "
-              f"occ {v.get('Occupancy')}")
+              f"occ {v.get('Occupancy')} scratch {v.get('ScratchSize')}")
