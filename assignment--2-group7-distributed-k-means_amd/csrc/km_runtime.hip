@@ -112,6 +112,20 @@ struct km_ctx {
   uint2* chg = nullptr;          // k_s1 change list, one segment per wave, {row, old << 16 | new}
   uint32_t* chg_cnt = nullptr;   // entries per wave segment (written by every delta k_s1)
   bool delta_ready = false;      // labels and stats_full describe one assignment
+  // row gate of k_s1's delta passes (km_s1_gate.h; allocated at the first
+  // gated pass): a row whose margin proves its label unchanged is not
+  // screened.  bounds_valid: the margins describe the labels in place (set by
+  // a gated pass, cleared by anything else that writes labels or replaces
+  // centroids); last_gated: the last assign with statistics went through the gate
+  km::S1GateBufs gt{nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool bounds_valid = false;
+  bool last_gated = false;
+  uint32_t gated_nw = 0;  // waves (work-list counts) of the last gated pass
+  bool gated_dense = false;  // ... which was the dense sweep with margins (every row)
+  // set by an update with the device repair armed: the word the repair raises
+  // when it replaces centroids (that iteration's DevStatus.repaired); the next
+  // gated pass of the batch then lists every row
+  const int32_t* gate_init_dev = nullptr;
   bool x3_stale = true;          // Chi/Clo/cn2s/bnd not made for the prepared centroids (ensure_x3)
   bool sweep_rev = false;        // the last k_assign_small / k_s1 launch swept the rows last-first
   int stats_pending = 0;         // the last assign left 0 nothing, 1 full sums, 2 deltas in stats
@@ -294,6 +308,13 @@ void free_centroids(km_ctx* c) {
   dfree(c->stats_full);
   dfree(c->chg);
   dfree(c->chg_cnt);
+  dfree(c->gt.marg);
+  dfree(c->gt.wl);
+  dfree(c->gt.wl_cnt);
+  dfree(c->gt.shift);
+  dfree(c->gt.cref);
+  c->bounds_valid = false;
+  c->last_gated = false;
   c->s1 = false;
   c->mdelta_geo = false;
   c->delta_ready = false;
@@ -557,6 +578,11 @@ int run_assign(km_ctx* c, bool with_stats) {
   }
   const bool sse = with_stats && c->want_sse;
   double* sse_slot = c->stats + (size_t)g.k * (g.d + 1);
+  // every assign writes labels; only a gated pass leaves margins that match them
+  const bool bounds_were_valid = c->bounds_valid;
+  c->bounds_valid = false;
+  if (!use_s1(c, with_stats)) c->gate_init_dev = nullptr;
+  if (with_stats) c->last_gated = false;
   if (with_stats && !c->stats_clean) KM_HIP(hipMemsetAsync(c->stats, 0, sizeof(double) * stats_len(g), c->stream));
   if (with_stats) c->stats_clean = false;
   if (c->path == 1) {
@@ -577,11 +603,40 @@ int run_assign(km_ctx* c, bool with_stats) {
     // compute_sse with delta statistics: residuals to the fp32 images c'
     // (k_s1, the resolvers), corrected by the update (km::launch_update corr)
     double* s1_sse = sse ? sse_slot : nullptr;
+    // the row gate: delta statistics without SSE (the residual needs every
+    // row) on the fused geometries with a gated instance.  Geometry and call
+    // sequence only: every rank takes the same path
+    const bool gated = with_stats && !s1_sse && c->fused && g.n > 0 && km::s1_gate_ok(g);
+    bool gdense = false;
+    if (gated) {
+      if (!c->gt.marg) {
+        KM_HIP(hipMalloc(&c->gt.marg, sizeof(float) * (size_t)g.n));
+        KM_HIP(hipMalloc(&c->gt.wl, sizeof(uint32_t) * km::s1_chg_entries(g, c->n_cu)));
+        KM_HIP(hipMalloc(&c->gt.wl_cnt, sizeof(uint32_t) * km::s1_wave_slots(c->n_cu)));
+        KM_HIP(hipMalloc(&c->gt.shift, sizeof(float) * ((size_t)g.k + 3)));
+        KM_HIP(hipMalloc(&c->gt.cref, sizeof(double) * (size_t)g.k * g.d));
+        KM_HIP(hipMemsetAsync(c->gt.cref, 0, sizeof(double) * (size_t)g.k * g.d, c->stream));
+      }
+      // no margins yet (known here): the dense sweep writes them, no list
+      gdense = !bounds_were_valid;
+      ProfScope ps(c, KM_K_PREP);
+      KM_HIP(km::launch_s1_gate(g, c->C64_cur, c->labels, c->gt, gdense ? 2 : 0, c->gate_init_dev, c->n_cu, c->gate,
+                                c->stream));
+    }
+    c->gate_init_dev = nullptr;
     {
       ProfScope ps(c, KM_K_ASSIGN, true);
+      // (the sweep direction alternates over the dense launches only)
       KM_HIP(km::launch_s1(c->X, c->xnorm, g, c->s1_img, c->s1_cn2o, c->s1_cft, c->s1_perm, c->s1_cst,
                            c->labels, c->queue, c->qcount, c->chg, c->chg_cnt, with_stats ? 1 : 0, c->n_cu,
-                           &c->ql, c->gate, c->stream, next_sweep(c), s1_sse));
+                           &c->ql, c->gate, c->stream, gated ? 0 : next_sweep(c), s1_sse,
+                           gated ? &c->gt : nullptr, gdense ? 1 : 0));
+    }
+    if (gated) {
+      c->bounds_valid = true;
+      c->last_gated = true;
+      c->gated_nw = c->ql.nwaves;
+      c->gated_dense = gdense;
     }
     {
       // the queued rows: near-ties of the re-scored candidates and the rows
@@ -818,6 +873,24 @@ int km_info_get(km_ctx* c, km_info* out) {
   return KM_OK;
 }
 
+int km_gated_rows(km_ctx* c, int64_t* out) {
+  KM_REQUIRE(c && out, KM_ERR_ARG, "null arg");
+  *out = -1;
+  if (!c->last_gated || !c->gt.wl_cnt || c->gated_nw == 0) return KM_OK;
+  if (c->gated_dense) {
+    *out = c->g.n;
+    return KM_OK;
+  }
+  KM_HIP(hipSetDevice(c->device));
+  std::vector<uint32_t> cnt(c->gated_nw);
+  KM_HIP(hipMemcpyAsync(cnt.data(), c->gt.wl_cnt, sizeof(uint32_t) * cnt.size(), hipMemcpyDeviceToHost, c->stream));
+  KM_HIP(hipStreamSynchronize(c->stream));
+  int64_t total = 0;
+  for (uint32_t v : cnt) total += v;
+  *out = total;
+  return KM_OK;
+}
+
 int km_load_begin(km_ctx* c, int64_t n, int32_t d) {
   KM_REQUIRE(c, KM_ERR_ARG, "null ctx");
   KM_REQUIRE(n >= 0 && n < (int64_t)UINT32_MAX, KM_ERR_ARG, "km_load_begin: n out of range");
@@ -863,6 +936,7 @@ int km_load_rows(km_ctx* c, int64_t row0, const float* rows, int64_t nrows) {
     if (rcf != KM_OK) return rcf;
   }
   c->delta_ready = false;  // the rows behind the labels change
+  c->bounds_valid = false;
   const int d = c->g.d, dp = c->g.dp;
   // double-buffered pinned staging: the host fills one half while the DMA
   // of the other is in flight (one event per half, one sync at the end)
@@ -1027,6 +1101,7 @@ int km_set_centroids(km_ctx* c, const double* C, int32_t k, int32_t d) {
   c->s1_color_age = 0;
   c->s1_batches = 0;
   c->delta_ready = false;
+  c->bounds_valid = false;
   c->stats_pending = 0;
   KM_HIP(hipMemcpyAsync(c->C64_cur, C, sizeof(double) * k * d, hipMemcpyHostToDevice, c->stream));
   int rc = prep(c);
@@ -1288,6 +1363,10 @@ int km_update_async(km_ctx* c, double tol, int64_t empty_seed) {
   }
   if (one) c->stats_clean = true;
   if (repair) {
+    // an armed device repair may replace centroids behind the update: the
+    // next gated pass of the batch lists every row if it did (a device word;
+    // km_batch_end reads it for the batch's last iteration)
+    c->gate_init_dev = &c->hist[slot].repaired;
     KM_REQUIRE(empty_seed >= 0, KM_ERR_ARG, "km_update_async: negative empty-cluster seed");
     const int rc = ensure_repair(c);
     if (rc != KM_OK) return rc;
@@ -1389,6 +1468,7 @@ int km_batch_end(km_ctx* c, km_status* st, int64_t* counts, int32_t* n_ran) {
   c->in_batch = false;
   c->batch_n = 0;
   c->rep_wait = false;  // an iteration left without its km_repair_apply_async did not run
+  c->gate_init_dev = nullptr;
   int ran = 0;
   while (ran < m && c->hist_host[ran].ran) ++ran;
   *n_ran = ran;
@@ -1412,6 +1492,7 @@ int km_batch_end(km_ctx* c, km_status* st, int64_t* counts, int32_t* n_ran) {
     // the iteration that raised the gate had its own prep gated too
     c->prep_of = c->hist_host[ran - 1].stop ? nullptr : c->C64_new;
     note_queue(c, c->hist_host[ran - 1]);
+    if (c->hist_host[ran - 1].repaired) c->bounds_valid = false;  // (its gate_init_dev word, read here)
     if (c->rep_enabled) {
       bool any_empty = false;
       for (int i = 0; i < ran; ++i) any_empty |= c->hist_host[i].n_empty > 0;
@@ -1451,6 +1532,7 @@ int km_replace_rows(km_ctx* c, const int32_t* ids, const double* rows, int32_t n
   }
   if (n == 0) return KM_OK;
   if (c->prep_of == c->C64_new) c->prep_of = nullptr;  // its images are stale now
+  c->bounds_valid = false;  // (host repair: the next delta pass screens every row)
   c->screen = c->screen_forced >= 0 ? c->screen_forced : km::KM_SCREEN_X3_REFINE;
   c->fast_blocked = false;
   c->rep_armed = c->rep_enabled;

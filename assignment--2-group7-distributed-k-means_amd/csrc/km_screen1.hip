@@ -54,6 +54,7 @@
 #include <float.h>
 
 #include "km_internal.h"
+#include "km_s1_gate.h"
 #include "km_s1_ring.h"
 
 namespace km {
@@ -118,6 +119,18 @@ constexpr size_t s1_lds_bytes(int ns2, int nb, bool table) {
          (s1_batched(ns2) ? (size_t)s1_waves(ns2, nb) * s1_ring(ns2, nb) * (dp * 4 + 16 + 128) : 0);
 }
 constexpr bool s1_table_global(int ns2, int nb) { return s1_lds_bytes(ns2, nb, true) > 160 * 1024; }
+// the delta-mode row gate (k_s1_gate and the gated instance of k_s1): 0 keeps
+// every delta pass dense (A/B arm).  The gated instance adds one float per
+// ring row to the LDS and exists where the batched re-score runs from the LDS
+// table, one tile per step
+#ifndef KM_S1_GATE
+#define KM_S1_GATE 1
+#endif
+constexpr size_t s1_gate_lds(int ns2, int nb) { return (size_t)s1_waves(ns2, nb) * s1_ring(ns2, nb) * 4; }
+constexpr bool s1_gated(int ns2, int nb) {
+  return KM_S1_GATE && s1_batched(ns2) && s1_tiles(ns2) == 1 && !s1_table_global(ns2, nb) &&
+         s1_lds_bytes(ns2, nb, true) + s1_gate_lds(ns2, nb) <= 160 * 1024;
+}
 
 
 __device__ __forceinline__ uint32_t f2u(float v) { return __float_as_uint(v); }
@@ -339,6 +352,11 @@ struct S1Args {
   uint32_t* chg_cnt;   // DELTA: entries per wave segment
   double* sse;         // SSE (MODE 1): every decided row's residual to the fp32 image c' of its centroid
   const int* gate;
+  // GATED: the rows to screen, [wave][seg] in row order with one count per
+  // wave (k_s1_gate), and the per-row margins (km_s1_gate.h)
+  const uint32_t* wl;
+  const uint32_t* wl_cnt;
+  float* marg;
 };
 
 // MODE 0: labels only (predict; every decided row's label written, queued
@@ -352,7 +370,13 @@ struct S1Args {
 // (launch_resolve sse_c32), and the update turns the total into
 // sum ||x - c||^2 with one exact per-cluster correction from the full sums
 // (k_update, sse_corr; DESIGN.md section 2 "Statistics and SSE").
-template <int NS2, int NB, int MODE, bool REV = false, bool SSE = false>
+// GATED (MODE 1, no REV, no SSE, the batched re-score): every row the kernel
+// decides gets a fresh margin (km_s1_gate.h), every row it queues margin 0 (it
+// is screened again next time).  GATED 1: a wave screens only the rows of its
+// segment of the gate's work list, 16 entries per tile.  GATED 2: the dense
+// sweep with margins, for the passes that the host knows must screen every
+// row (no margins yet): no gate pass, no indirection.
+template <int NS2, int NB, int MODE, bool REV = false, bool SSE = false, int GATED = 0>
 __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void k_s1(S1Args A) {
   if (*A.gate) return;  // a stopped batch (km_update_async): the rest of it is a no-op
   constexpr int S1_WAVES = s1_waves(NS2, NB);
@@ -361,6 +385,9 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
   // arithmetic is checked exhaustively for both ring sizes at compile time)
   static_assert(S1_RING == 12 || S1_RING == 16, "ring sizes covered by s1_ring_check");
   static_assert(16 <= 2 * S1_RING && S1_TILE_ROWS == 16, "a tile may complete at most two batches");
+  static_assert(!GATED || (MODE == 1 && !REV && !SSE && s1_batched(NS2)), "the gated instance: delta mode, batched");
+  constexpr bool LIST = GATED == 1;  // rows from the work list
+  constexpr bool MARG = GATED != 0;  // margins written
   constexpr int DP = 32 * NS2;
   constexpr int FQ = 8 * NS2;  // features per quarter lane
   constexpr int KP = 32 * NB;
@@ -385,6 +412,8 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
   float* sRx = reinterpret_cast<float*>(sPerm + NT);                   // [S1_WAVES][S1_RING][DP]
   uint4* sRm = reinterpret_cast<uint4*>(sRx + S1_WAVES * S1_RING * DP);  // [S1_WAVES][S1_RING]
   float4* sRh = reinterpret_cast<float4*>(sRm + S1_WAVES * S1_RING);     // [S1_WAVES][S1_RING][4][2]
+  // GATED: the ring rows' lower bound of the distance to every non-candidate
+  float* sRl = reinterpret_cast<float*>(sRh + S1_WAVES * S1_RING * 8);   // [S1_WAVES][S1_RING]
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -445,13 +474,34 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
     float4 x[FQ / 4];
     float xn;
     int32_t old;
+    uint32_t row;  // LIST: the tile's row of this lane (>= n: none)
   };
+  // LIST: this wave's work-list segment; the entry of the next tile to load
+  // is fetched one load ahead of its row, so the two dependent loads of a
+  // tile (entry, then row) never wait for each other in the loop
+  const uint32_t* wlp = nullptr;
+  uint32_t wln = 0, wnext = 0xFFFFFFFFu;
+  const bool gscale = MARG && s1g_scale_ok(s);
+  if constexpr (LIST) {
+    wlp = A.wl + (size_t)gw * A.seg;
+    wln = min(A.wl_cnt[gw], A.seg);
+    wnext = (uint32_t)c16 < wln ? wlp[c16] : 0xFFFFFFFFu;
+  }
   // serpentine sweep (REV: its own instance, since a run-time select in the
   // row arithmetic cost the issue-bound c3 kernel 1.5%): step tiles mapped
   // last-first; tiles past the end stay past the end
   auto tmap = [&](uint32_t t) { return (REV && t < ntiles) ? ntiles - 1u - t : t; };
   auto load = [&](uint32_t tile, Buf& B) {
-    const uint32_t row = tmap(tile) * 16u + (uint32_t)c16;
+    uint32_t row;
+    if constexpr (LIST) {
+      // (tiles are loaded in order 0, 1, 2, ...: wnext is tile's entry)
+      row = wnext;
+      const uint32_t e = (tile + 1u) * 16u + (uint32_t)c16;
+      wnext = e < wln ? wlp[e] : 0xFFFFFFFFu;
+      B.row = row;
+    } else {
+      row = tmap(tile) * 16u + (uint32_t)c16;
+    }
     const uint32_t rr = row < n ? row : (n - 1u);
     const float4* xr = reinterpret_cast<const float4*>(A.X + (size_t)rr * DP + FQ * q);
 #pragma unroll
@@ -472,7 +522,7 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
   // hardware sqrt loses accuracy: U takes sqrt(2^-96) (an over-estimate), L
   // takes 0 (an under-estimate)
   auto decide = [&](bool act0, uint32_t cnt, const uint32_t* sl, const float4* xv, int32_t& lab1, int32_t& lab2,
-                    uint32_t& kind, uint32_t& ws) {
+                    uint32_t& kind, uint32_t& ws, float& ubw, float& lbo) {
     auto partial = [&](uint32_t slot) {
       const float4* cp = TG ? reinterpret_cast<const float4*>(A.cft + slot * CS + FQ * q)
                             : reinterpret_cast<const float4*>(sCf + slot * CS + FQ * q);
@@ -540,6 +590,8 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
       lab2 = l2;
       kind = kd;
       ws = s1;  // the winner's table slot (SSE residual)
+      ubw = U1;  // GATED: the winner's upper bound, the other candidates' smallest lower bound
+      lbo = Lo;
     }
   };
   // a row's outcome (every lane of its quad calls with the same values):
@@ -619,9 +671,17 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
       }
       int32_t lab1 = 0, lab2 = 0;
       uint32_t kind = 2u, ws = 0u;
-      decide(act, cnt, sl, xv, lab1, lab2, kind, ws);
+      float ubw = 0.0f, lbo = 0.0f;
+      decide(act, cnt, sl, xv, lab1, lab2, kind, ws, ubw, lbo);
       emit(act, mt.x, kind, lab1, lab2, (int32_t)(mt.y & 0xFFFFu));
       resid(act && kind == 0u, ws, xv);
+      if constexpr (MARG) {
+        // a decided row: the winner against the other candidates (Lo) and
+        // against everything above the threshold (the tile's bound from T);
+        // a queued one: 0
+        if (act && q == 0)
+          A.marg[mt.x] = (kind == 0u && gscale) ? s1g_margin(fminf(lbo, sRl[wave * S1_RING + slot]), ubw) : 0.0f;
+      }
     } else {
       (void)nb;
     }
@@ -630,7 +690,7 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
   // everything after the chains of one tile: certificate, labels, queue,
   // re-scoring ring
   auto tail = [&](uint32_t tile, const Buf& B, const float (&h)[2][4], float h2m) {
-    const uint32_t row = tmap(tile) * 16u + (uint32_t)c16;
+    const uint32_t row = LIST ? B.row : tmap(tile) * 16u + (uint32_t)c16;
     const bool valid = row < n;
     // full slot ids in the heads, (chain << MB) | member: distinct keys, so
     // float comparisons order them totally (f32 denormals are kept, and +0
@@ -715,6 +775,32 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
     emit(valid, row, dec1 || needy ? 0u : 2u, labm, 0, old);
     return;
 #endif
+    float lbT = 0.0f;  // MARG: lower bound of the distance to every centroid whose key is above T
+    if constexpr (MARG) {
+      // fresh margins (km_s1_gate.h).  ||x||^2 in fp32 over the quad; the
+      // smallest key of any centroid but the argmin: the second smallest head
+      // or a chain's second key (distinct keys: the heads above m)
+      float xs = 0.0f;
+#pragma unroll
+      for (int u = 0; u < FQ / 4; ++u) {
+        xs = fmaf(B.x[u].x, B.x[u].x, xs);
+        xs = fmaf(B.x[u].y, B.x[u].y, xs);
+        xs = fmaf(B.x[u].z, B.x[u].z, xs);
+        xs = fmaf(B.x[u].w, B.x[u].w, xs);
+      }
+      const S1GRow gr = s1g_row(s, E, quad_sum(xs));
+      float nl = h2m;
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) nl = min_raw(nl, hk[cb][i] > m ? hk[cb][i] : FLT_MAX);
+      const float h2 = quad_min(nl);
+      lbT = s1g_lb(T, RP, gr);
+      // (rows with 2 .. LMAX candidates get theirs from the re-score; the
+      // rest of the undecided rows are queued: 0)
+      if (valid && !needy && q == 0)
+        A.marg[row] = (dec1 && gscale) ? s1g_margin(s1g_lb(h2, RP, gr), s1g_ub(m, RP, gr)) : 0.0f;
+    }
     if constexpr (BATCH) {
       emit(valid && !needy, row, dec1 ? 0u : 2u, labm, 0, old);
       resid(dec1, sm, B.x);
@@ -736,6 +822,8 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
           float4* hp = sRh + ((wave * S1_RING + slot) * 4 + q) * 2;
           hp[0] = make_float4(hk[0][0], hk[0][1], hk[0][2], hk[0][3]);
           hp[1] = make_float4(hk[1][0], hk[1][1], hk[1][2], hk[1][3]);
+          if constexpr (MARG)
+            if (q == 0) sRl[wave * S1_RING + slot] = lbT;
         };
         // a tile that leaves room: its rows go behind the rows carried in
         // (batch 0 of s1_ring_slot, km_s1_ring.h: slot rc + rk).  A tile that
@@ -781,6 +869,9 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
       sl[0] = sm;
       sl[1] = f2u(lb) & SLOTM;
       float prev = lb;
+      float ubw = 0.0f, lbo = 0.0f;
+      (void)ubw;
+      (void)lbo;
 #pragma unroll
       for (int r = 2; r < S1_LMAX; ++r) {
         sl[r] = 0u;
@@ -795,7 +886,7 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
       }
       int32_t lab1 = labm, lab2 = 0;
       uint32_t kind = dec1 ? 0u : 2u, ws = sm;
-      if (__ballot(needy) != 0ull) decide(needy, cnt, sl, B.x, lab1, lab2, kind, ws);
+      if (__ballot(needy) != 0ull) decide(needy, cnt, sl, B.x, lab1, lab2, kind, ws, ubw, lbo);
       emit(valid, row, kind, lab1, lab2, old);
       resid(valid && kind == 0u, ws, B.x);
     }
@@ -974,23 +1065,27 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
   // buffers of rows: NBUF - 1 steps' loads in flight while one is processed
   // (loads past the end read row n - 1 and are never used)
   constexpr int NBUF = KM_S1_NBUF > 0 ? KM_S1_NBUF : (NS2 == 1 && NB > 8 && S1_WAVES == 8 ? 3 : 2);
-  const uint32_t nst = (ntiles + (uint32_t)TT - 1u) / (uint32_t)TT;
+  static_assert(!LIST || TT == 1, "the gated instance walks its list one tile per step");
+  // steps st0, st0 + sw, ... below nst: the wave's share of the tiles, or
+  // (GATED) the tiles of its own work list
+  const uint32_t nst = LIST ? (wln + 15u) / 16u : (ntiles + (uint32_t)TT - 1u) / (uint32_t)TT;
+  const uint32_t st0 = LIST ? 0u : gw, sw = LIST ? 1u : nw;
   Buf b[NBUF][TT];
   auto load_step = [&](uint32_t st, Buf (&BB)[TT]) {
 #pragma unroll
     for (int u = 0; u < TT; ++u) load(st * TT + (uint32_t)u, BB[u]);
   };
 #pragma unroll
-  for (int u = 0; u + 1 < NBUF; ++u) load_step(gw + (uint32_t)u * nw, b[u]);
+  for (int u = 0; u + 1 < NBUF; ++u) load_step(st0 + (uint32_t)u * sw, b[u]);
   // (st + 2 NBUF nw stays below 2^32: ntiles < 2^28, nw < 2^16)
-  for (uint32_t st = gw; st < nst; st += (uint32_t)NBUF * nw) {
+  for (uint32_t st = st0; st < nst; st += (uint32_t)NBUF * sw) {
     bool done = false;
 #pragma unroll
     for (int u = 0; u < NBUF; ++u) {
       if (!done) {
-        load_step(st + (uint32_t)(u + NBUF - 1) * nw, b[(u + NBUF - 1) % NBUF]);
-        process(st + (uint32_t)u * nw, b[u]);
-        done = st + (uint32_t)(u + 1) * nw >= nst;
+        load_step(st + (uint32_t)(u + NBUF - 1) * sw, b[(u + NBUF - 1) % NBUF]);
+        process(st + (uint32_t)u * sw, b[u]);
+        done = st + (uint32_t)(u + 1) * sw >= nst;
       }
     }
     if (done) break;
@@ -1006,6 +1101,129 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
     for (int o = 32; o >= 1; o >>= 1) ssa += __shfl_xor(ssa, o);
     if (lane == 0 && ssa != 0.0) atomicAdd(A.sse, ssa);
   }
+}
+
+// ---------------------------------------------------------------------------
+// Row gate of the delta fit (km_s1_gate.h; DESIGN.md section 2 "Row gate").
+//
+// k_s1_shift (one workgroup, before every gated assign): shift[j] = the
+// distance of centroid j from where it stood when the margins were last
+// brought up to date (cref, a copy kept for this purpose alone, so that
+// whatever moved the centroids in between -- the update, a repair, new
+// centroids -- is covered), rounded up; then the largest shift, the second
+// largest and the largest one's index in shift[k .. k + 2]; cref = C.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_s1_shift(const double* __restrict__ C, double* __restrict__ cref, int k,
+                                                   int d, float* __restrict__ shift, const int* __restrict__ gate) {
+  if (*gate) return;
+  __shared__ float sv[1024];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwv = blockDim.x >> 6;
+  for (int j = wave; j < k; j += nwv) {
+    double sh = 0.0;
+    for (int f = lane; f < d; f += 64) {
+      const double a = C[(size_t)j * d + f];
+      const double df = a - cref[(size_t)j * d + f];
+      sh = fma(df, df, sh);
+      cref[(size_t)j * d + f] = a;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) sh += __shfl_xor(sh, o);
+    if (lane == 0) {
+      const float v = s1g_shift(sh);
+      sv[j] = v;
+      shift[j] = v;
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {
+    // (m1, a1): the largest shift and its index; m2: the largest of the rest
+    // (equal to m1 when two centroids tie, whichever index a1 then names)
+    float m1 = -1.0f, m2 = -1.0f;
+    int a1 = 0;
+    for (int j = lane; j < k; j += 64) {
+      const float v = sv[j];
+      m2 = v > m1 ? m1 : fmaxf(m2, v);
+      a1 = v > m1 ? j : a1;
+      m1 = v > m1 ? v : m1;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const float om1 = __shfl_xor(m1, o), om2 = __shfl_xor(m2, o);
+      const int oa1 = __shfl_xor(a1, o);
+      m2 = fmaxf(fminf(m1, om1), fmaxf(m2, om2));
+      a1 = om1 > m1 ? oa1 : a1;
+      m1 = fmaxf(m1, om1);
+    }
+    if (lane == 0) {
+      shift[k] = m1;
+      shift[k + 1] = fmaxf(m2, 0.0f);  // (k = 1: no other centroid moves)
+      shift[k + 2] = __int_as_float(a1);
+    }
+  }
+}
+
+// k_s1_gate: k_s1's grid; wave w owns rows [w seg, (w + 1) seg).  Per row the
+// margin takes one step (s1g_step) and is written back; a row whose margin is
+// not strictly positive (or not a number) is written 0 and appended to the
+// wave's segment of the work list -- ballot and popcount, in row order, one
+// count per wave, no atomics: the list, and so the order in which the change
+// list and the float64 sums see the rows, is the same on every run.  `init`
+// (no margins yet, or labels not k_s1's): every row is listed.
+struct S1GateArgs {
+  const int32_t* labels;
+  float* marg;
+  int64_t n;
+  int k;
+  uint32_t seg;
+  const float* shift;  // [k + 3] (k_s1_shift)
+  uint32_t* wl;
+  uint32_t* wl_cnt;
+  int init;
+  const int32_t* init_dev;  // or nullptr: a device word that also asks for every row (a repair replaced centroids)
+  const int* gate;
+};
+
+template <int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void k_s1_gate(S1GateArgs A) {
+  if (*A.gate) return;
+  __shared__ float sSh[1024];
+  for (int i = threadIdx.x; i < A.k; i += WAVES * 64) sSh[i] = A.shift[i];
+  const float top1 = A.shift[A.k], top2 = A.shift[A.k + 1];
+  const uint32_t atop = (uint32_t)__float_as_int(A.shift[A.k + 2]);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t gw = blockIdx.x * WAVES + wave;
+  const uint64_t n = (uint64_t)A.n;
+  const uint64_t r0 = (uint64_t)gw * A.seg, r1 = min(n, r0 + A.seg);
+  uint32_t* wl = A.wl + (size_t)gw * A.seg;
+  const uint64_t below = (1ull << lane) - 1ull;
+  const bool init = A.init != 0 || (A.init_dev && *A.init_dev != 0);
+  uint32_t cnt = 0;
+  constexpr int G = 4;  // chunks of 64 rows in flight
+  for (uint64_t base = r0; base < r1; base += 64 * G) {
+    int32_t lab[G];
+    float mg[G];
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      const uint64_t row = base + 64 * u + lane;
+      const bool in = row < r1;
+      lab[u] = (in && !init) ? A.labels[row] : 0;
+      mg[u] = (in && !init) ? A.marg[row] : 0.0f;
+    }
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      const uint64_t row = base + 64 * u + lane;
+      const bool in = row < r1;
+      const uint32_t l = min((uint32_t)lab[u], (uint32_t)(A.k - 1));
+      const float m2 = s1g_step(mg[u], sSh[l], l == atop ? top2 : top1);
+      const bool keep = !init && m2 > 0.0f;
+      if (in) A.marg[row] = keep ? m2 : 0.0f;
+      const uint64_t mask = __ballot(in && !keep);
+      if (in && !keep) wl[cnt + (uint32_t)__popcll(mask & below)] = (uint32_t)row;
+      cnt += (uint32_t)__popcll(mask);
+    }
+  }
+  if (lane == 0) A.wl_cnt[gw] = cnt;
 }
 
 // Delta statistics (km_runtime.hip): mode 1 folds an iteration's all-reduced
@@ -1304,10 +1522,55 @@ hipError_t launch_s1_prep(const double* C64, const float* C32, const Geometry& g
   return hipGetLastError();
 }
 
+// the gated instance where the geometry has one (s1_gate_ok)
+template <int NS2, int NB>
+static void launch_s1_gated(int nbk, size_t lds, hipStream_t s, const S1Args& a, bool dense) {
+  if constexpr (s1_gated(NS2, NB)) {
+    if (dense)
+      KM_TIMED_LAUNCH((k_s1<NS2, NB, 1, false, false, 2>), dim3(nbk), dim3(s1_waves(NS2, NB) * 64),
+                      lds + s1_gate_lds(NS2, NB), s, a);
+    else
+      KM_TIMED_LAUNCH((k_s1<NS2, NB, 1, false, false, 1>), dim3(nbk), dim3(s1_waves(NS2, NB) * 64),
+                      lds + s1_gate_lds(NS2, NB), s, a);
+  }
+}
+
+bool s1_gate_ok(const Geometry& g) {
+  if (!s1_ok(g) || g.k > 1024) return false;
+  const int ns2 = g.dp / 32, nb = g.kp / 32;
+  switch (ns2 * 100 + nb) {
+    case 202: case 204: case 206: case 208:
+    case 102: case 104: case 106: case 108: case 112: case 116:
+      return s1_gated(ns2, nb);
+    default:
+      return false;
+  }
+}
+
+hipError_t launch_s1_gate(const Geometry& g, const double* C64, const int32_t* labels, const S1GateBufs& b, int init,
+                          const int32_t* init_dev, int n_cu, const int* gate, hipStream_t s) {
+  if (g.n == 0) return hipSuccess;
+  if (!s1_gate_ok(g)) return hipErrorInvalidValue;
+  int nbk;
+  uint32_t seg;
+  (void)s1_grid(g, n_cu, &nbk, &seg);
+  hipLaunchKernelGGL(k_s1_shift, dim3(1), dim3(1024), 0, s, C64, b.cref, g.k, g.d, b.shift, gate);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (init == 2) return hipSuccess;  // the dense sweep with margins follows: no list
+  S1GateArgs a{labels, b.marg, g.n, g.k, seg, b.shift, b.wl, b.wl_cnt, init, init_dev, gate};
+  if (s1_geo_waves(g) == 12)
+    hipLaunchKernelGGL(k_s1_gate<12>, dim3(nbk), dim3(12 * 64), 0, s, a);
+  else
+    hipLaunchKernelGGL(k_s1_gate<8>, dim3(nbk), dim3(8 * 64), 0, s, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_s1(const float* X, const float* xnorm, const Geometry& g, const uint4* img, const float* cn2o,
                      const float* cft, const int32_t* perm, const float* cst, int32_t* labels,
                      QEntry* queue, uint32_t* qcount, uint2* chg, uint32_t* chg_cnt, int delta, int n_cu,
-                     QLayout* ql, const int* gate, hipStream_t s, int rev, double* sse) {
+                     QLayout* ql, const int* gate, hipStream_t s, int rev, double* sse, const S1GateBufs* gt,
+                     int gdense) {
   ql->seg = 0;
   ql->nwaves = 0;
   if (g.n == 0) return hipSuccess;
@@ -1319,13 +1582,17 @@ hipError_t launch_s1(const float* X, const float* xnorm, const Geometry& g, cons
   ql->seg = seg;
   ql->nwaves = (uint32_t)nw;
   if (sse && !delta) return hipErrorInvalidValue;  // residuals ride with delta statistics only
-  S1Args a{X, xnorm, g.n, g.k, g.d, seg, img, cn2o, cft, perm, cst, labels, queue, qcount, chg, chg_cnt, sse, gate};
+  S1Args a{X, xnorm, g.n, g.k, g.d, seg, img, cn2o, cft, perm, cst, labels, queue, qcount, chg, chg_cnt, sse, gate,
+           gt ? gt->wl : nullptr, gt ? gt->wl_cnt : nullptr, gt ? gt->marg : nullptr};
+  if (gt && (!delta || sse || !s1_gate_ok(g))) return hipErrorInvalidValue;
   const size_t lds = s1_lds_bytes(sg.ns2, sg.nb, !s1_table_global(sg.ns2, sg.nb));
   if (lds > 160 * 1024) return hipErrorInvalidValue;
   (void)nt;
 #define KM_S1_CASE(NS2_, NB_)                                                                                   \
   case NS2_ * 100 + NB_:                                                                                        \
-    if (delta && sse)                                                                                           \
+    if (gt)                                                                                                     \
+      launch_s1_gated<NS2_, NB_>(nbk, lds, s, a, gdense != 0);                                                             \
+    else if (delta && sse)                                                                                      \
       KM_TIMED_LAUNCH((k_s1<NS2_, NB_, 1, false, true>), dim3(nbk), dim3(s1_waves(NS2_, NB_) * 64), lds, s, a); \
     else if (delta && rev && KM_S1_SERP && NS2_ == 2 && NB_ == 8)                                               \
       KM_TIMED_LAUNCH((k_s1<2, 8, 1, true>), dim3(nbk), dim3(s1_waves(2, 8) * 64), lds, s, a);                  \

@@ -286,7 +286,12 @@ class HipEngine:
     def info(self) -> dict:
         inf = _lib.KmInfo()
         self._c(self.lib.km_info_get(self.ctx, ctypes.byref(inf)), "km_info_get")
-        return {f: getattr(inf, f) for f, _ in inf._fields_}
+        out = {f: getattr(inf, f) for f, _ in inf._fields_}
+        # rows the last assign with statistics screened (-1: not gated); km_gated_rows
+        rows = ctypes.c_int64(-1)
+        self._c(self.lib.km_gated_rows(self.ctx, ctypes.byref(rows)), "km_gated_rows")
+        out["gated_rows"] = rows.value
+        return out
 
     # -- profiling ---------------------------------------------------------------
     _PHASES = {"assign": 0, "resolve": 1, "stats": 2, "update": 3, "prep": 4}   # KM_K_* (kmeans_amd.h)

@@ -101,6 +101,15 @@ int km_destroy(km_ctx* ctx);
 int km_set_stream(km_ctx* ctx, void* hip_stream);
 int km_sync(km_ctx* ctx);
 int km_info_get(km_ctx* ctx, km_info* out);
+/* Row gate of the delta statistics (fused k_s1 geometries, compute_sse off):
+ * a row whose stored margin proves that its label cannot have changed since
+ * the previous assignment is not screened at all.  *out = the rows the last
+ * km_assign_stats did screen (n on the first gated pass and after anything
+ * that invalidates the margins: new centroids or rows, a predict, a full
+ * statistics pass, an empty-cluster repair), or -1 when that pass was not
+ * gated.  Synchronises the stream.  (Added within ABI 6: a new entry point,
+ * no existing layout changes.) */
+int km_gated_rows(km_ctx* ctx, int64_t* out);
 
 /* Materialise this rank's rows in HBM once: replaces sc.parallelize(X) +
  * rdd.cache() (kmeans_spark.py:256, 369, 418, 471, 518, 568).  km_load_begin
