@@ -245,22 +245,25 @@ hipError_t launch_s1(const float* X, const float* xnorm, const Geometry& g, cons
                      QEntry* queue, uint32_t* qcount, uint2* chg, uint32_t* chg_cnt, int delta, int n_cu,
                      QLayout* ql, const int* gate, hipStream_t s, int rev = 0, double* sse = nullptr,
                      const S1GateBufs* gt = nullptr, int gdense = 0);
-// Row gate of the delta fit (km_s1_gate.h): per-row margins, the work list
-// ([wave][seg] rows, s1_chg_entries of them, and s1_wave_slots counts), the
-// centroid shifts [k + 3] and the centroids the margins refer to [k][d]
+// Row gate of the delta fit (km_s1_gate.h): per-row bases (fresh margin plus
+// the label's lower total), the work list ([wave][seg] entries {row, label},
+// s1_chg_entries of them, and s1_wave_slots counts), the centroids the
+// margins refer to [k][d], the clusters' running totals [k] and their float
+// images [2 k] (upper, then lower)
 struct S1GateBufs {
   float* marg;
-  uint32_t* wl;
+  uint2* wl;
   uint32_t* wl_cnt;
-  float* shift;
   double* cref;
+  double* acc;
+  float* accud;
 };
 // the geometry has a gated instance of k_s1 (delta statistics, no SSE)
 bool s1_gate_ok(const Geometry& g);
-// shifts since the last gated pass (cref := C64), then the gate: margins
-// stepped, the rows to screen listed per wave (init 1, or *init_dev != 0:
-// every row).  init 2: the shifts only -- launch_s1 with gdense follows, the
-// dense sweep that writes every row's margin
+// shifts since the last gated pass (cref := C64) added to the running totals,
+// then the gate: the rows to screen listed per wave (init 1, or *init_dev !=
+// 0: every row).  init 2: the shifts only, the totals back to 0 -- launch_s1
+// with gdense follows, the dense sweep that writes every row's margin
 hipError_t launch_s1_gate(const Geometry& g, const double* C64, const int32_t* labels, const S1GateBufs& b, int init,
                           const int32_t* init_dev, int n_cu, const int* gate, hipStream_t s);
 // k_s1's change list: entries (wave segments) and per-wave counts to allocate

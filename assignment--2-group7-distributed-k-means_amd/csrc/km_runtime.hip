@@ -117,7 +117,7 @@ struct km_ctx {
   // screened.  bounds_valid: the margins describe the labels in place (set by
   // a gated pass, cleared by anything else that writes labels or replaces
   // centroids); last_gated: the last assign with statistics went through the gate
-  km::S1GateBufs gt{nullptr, nullptr, nullptr, nullptr, nullptr};
+  km::S1GateBufs gt{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   bool bounds_valid = false;
   bool last_gated = false;
   uint32_t gated_nw = 0;  // waves (work-list counts) of the last gated pass
@@ -311,8 +311,9 @@ void free_centroids(km_ctx* c) {
   dfree(c->gt.marg);
   dfree(c->gt.wl);
   dfree(c->gt.wl_cnt);
-  dfree(c->gt.shift);
   dfree(c->gt.cref);
+  dfree(c->gt.acc);
+  dfree(c->gt.accud);
   c->bounds_valid = false;
   c->last_gated = false;
   c->s1 = false;
@@ -611,11 +612,14 @@ int run_assign(km_ctx* c, bool with_stats) {
     if (gated) {
       if (!c->gt.marg) {
         KM_HIP(hipMalloc(&c->gt.marg, sizeof(float) * (size_t)g.n));
-        KM_HIP(hipMalloc(&c->gt.wl, sizeof(uint32_t) * km::s1_chg_entries(g, c->n_cu)));
+        KM_HIP(hipMalloc(&c->gt.wl, sizeof(uint2) * km::s1_chg_entries(g, c->n_cu)));
         KM_HIP(hipMalloc(&c->gt.wl_cnt, sizeof(uint32_t) * km::s1_wave_slots(c->n_cu)));
-        KM_HIP(hipMalloc(&c->gt.shift, sizeof(float) * ((size_t)g.k + 3)));
         KM_HIP(hipMalloc(&c->gt.cref, sizeof(double) * (size_t)g.k * g.d));
         KM_HIP(hipMemsetAsync(c->gt.cref, 0, sizeof(double) * (size_t)g.k * g.d, c->stream));
+        KM_HIP(hipMalloc(&c->gt.acc, sizeof(double) * (size_t)g.k));
+        KM_HIP(hipMalloc(&c->gt.accud, sizeof(float) * 2 * (size_t)g.k));
+        KM_HIP(hipMemsetAsync(c->gt.acc, 0, sizeof(double) * (size_t)g.k, c->stream));
+        KM_HIP(hipMemsetAsync(c->gt.accud, 0, sizeof(float) * 2 * (size_t)g.k, c->stream));
       }
       // no margins yet (known here): the dense sweep writes them, no list
       gdense = !bounds_were_valid;

@@ -20,8 +20,34 @@
 // appear; s1g_margin maps both to 0, and the gate lists every row whose
 // margin is not > 0.
 //
-// Plain C++ (no HIP headers): tests/test_host_s1_gate.py compiles it into a
-// host program and checks the certificate in float64.
+// Accumulated-drift form (what the kernels store).  Stepping every margin
+// every pass means writing every margin every pass.  Instead the runtime keeps
+// one running total per cluster,
+//   acc[j] = sum over the gated passes of (shift[j] + largest other shift),
+// since the margins' epoch began (a dense pass that rewrites every margin, or
+// a pass with a non-finite shift, which lists every row: acc = 0 again), and a
+// row stores base = round_down(marg_fresh + acc_dn[label]) with acc_dn <= acc
+// at the time its margin was fresh.  The gate's test is the bare comparison
+//   base > acc_up[label],  acc_up >= acc now,
+// no arithmetic, no rounding, nothing written back.  Proof (real arithmetic;
+// `then`: when the margin was fresh; the label has not changed since, or the
+// row would have been listed and given a new base):
+//   marg_now >= marg_fresh - (acc_now - acc_then)      (the steps' sum; every
+//                                         accumulation is rounded up)
+//            >= (base - acc_dn_then) + acc_then - acc_now   (base rounded down)
+//            >= base - acc_now >= base - acc_up_now > 0.
+// A queued, non-finite or undecided row stores 0, and acc_up > 0 always, so it
+// is listed.  acc is float64, each addition rounded up by 1 + 2^-50, and is
+// published as two floats per pass (s1g_acc_up, s1g_acc_dn: one float ulp of
+// acc either way).  Why not a float total rounded by s1g_up: its 8 u relative
+// inflation of acc ~ 50 is 2.5e-5 per pass, more than the real shifts of a
+// converged fit, so every row would slowly be listed again; the float64 form's
+// error is constant, one ulp of acc.  A non-finite shift makes acc_up +inf:
+// the comparison fails for every row.
+//
+// Plain C++ (no HIP headers): tests/test_host_s1_gate.py and
+// tests/test_host_s1_gate_acc.py compile it into host programs and check the
+// certificate in float64.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -115,6 +141,68 @@ KM_S1G_FN float s1g_lb(float key, float rp, const S1GRow& r) {
 KM_S1G_FN float s1g_margin(float lb, float ub) {
   const float m = s1g_dn(lb - ub);
   return (fabsf(m) <= 3.0e38f) ? m : 0.0f;
+}
+
+// --- accumulated-drift form -------------------------------------------------
+// one pass's step added to a cluster's running total (sl: its own shift, so:
+// the largest shift of any other centroid; both >= 0 or +inf from s1g_shift).
+// The two float64 additions lose at most 2^-52 relative, the factor puts back
+// 2^-50: the result is >= the real sum.  +inf (and NaN) stay non-finite
+KM_S1G_FN double s1g_acc_add(double acc, float sl, float so) {
+  return (acc + ((double)sl + (double)so)) * (1.0 + 0x1p-50);
+}
+// acc as a float from above: the conversion's half ulp is inside the 2^-23
+// (s1g_shift's form); anything non-finite or beyond the float range: +inf
+KM_S1G_FN float s1g_acc_up(double acc) {
+  const float f = (float)acc;
+  const float r = fmaf(f, 0x1p-23f, f) + S1G_TINY;
+  return (r <= 3.0e38f) ? r : INFINITY;
+}
+// acc as a float from below (f - f 2^-23 is at least one ulp under f, which is
+// within half an ulp of acc), never negative; non-finite acc: 0, a lower bound
+KM_S1G_FN float s1g_acc_dn(double acc) {
+  if (!(acc <= 3.0e38)) return 0.0f;
+  const float f = (float)acc;
+  const float r = fmaf(f, -0x1p-23f, f) - S1G_TINY;
+  return r > 0.0f ? r : 0.0f;
+}
+// one cluster's total over one gated pass, with the two images published for
+// it (k_s1_shift runs this per cluster).  sl, so as in s1g_acc_add; top: the
+// pass's largest shift.  `reset`: every margin is rewritten by the pass (the
+// dense sweep): a new epoch, acc = 0.  A non-finite top shift also starts a
+// new epoch, but with the upper image +inf for this pass: the gate lists
+// every row, every listed row gets a new base against the lower image 0, and
+// the totals are finite again afterwards (as a stepped margin would be).
+// A large FINITE shift does not: it stays in acc until the next dense sweep,
+// and from then on a row is kept only while its fresh margin exceeds the
+// width acc_up - acc_dn, about two float ulps of acc.  That is always safe,
+// but a move that is huge against the data's scale (1e30, say) leaves every
+// row listed at every pass until new centroids or rows start a new epoch,
+// where a stepped margin recovered after one pass.  Lloyd's own moves shrink,
+// and acc stays within a small multiple of the first moves
+KM_S1G_FN double s1g_acc_pass(double acc, float sl, float so, float top, bool reset, float* up, float* dn) {
+  const bool wild = !(top <= 3.0e38f);
+  const double a = (reset || wild) ? 0.0 : s1g_acc_add(acc, sl, so);
+  *up = (wild && !reset) ? INFINITY : s1g_acc_up(a);
+  *dn = s1g_acc_dn(a);
+  return a;
+}
+// what a decided row stores: its fresh margin (s1g_margin: finite) plus the
+// lower total of its label, rounded down; 0 (listed next time) if that is not
+// a finite number
+KM_S1G_FN float s1g_base(float marg, float acc_dn) {
+  const float b = s1g_dn(marg + acc_dn);
+  return (fabsf(b) <= 3.0e38f) ? b : 0.0f;
+}
+// the gate's test: the row keeps its label and is not screened
+KM_S1G_FN bool s1g_keep(float base, float acc_up) { return base > acc_up; }
+
+// upper bound of ||x|| from the fp32 sum of the row's squares (s1g_row's xhi,
+// the root rounded up twice as in s1g_ub); NaN stays NaN, overflow gives +inf
+KM_S1G_FN float s1g_xnorm(float xs) {
+  float v = s1g_up(xs * (1.0f + 64.0f * S1G_U));
+  v = !(v < 0x1p-96f) ? v : 0x1p-96f;
+  return s1g_up(s1g_up(s1g_sqrt(v)));
 }
 
 }  // namespace km

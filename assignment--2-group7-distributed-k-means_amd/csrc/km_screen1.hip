@@ -53,6 +53,8 @@
 //     float64 by k_rerank2; kind 2: full float64 scan by k_fullscan).
 #include <float.h>
 
+#include <type_traits>
+
 #include "km_internal.h"
 #include "km_s1_gate.h"
 #include "km_s1_ring.h"
@@ -352,11 +354,14 @@ struct S1Args {
   uint32_t* chg_cnt;   // DELTA: entries per wave segment
   double* sse;         // SSE (MODE 1): every decided row's residual to the fp32 image c' of its centroid
   const int* gate;
-  // GATED: the rows to screen, [wave][seg] in row order with one count per
-  // wave (k_s1_gate), and the per-row margins (km_s1_gate.h)
-  const uint32_t* wl;
+  // GATED: the rows to screen with the labels they hold, {row, old},
+  // [wave][seg] in row order with one count per wave (k_s1_gate), the per-row
+  // bases and the clusters' lower totals they are stored against [k]
+  // (km_s1_gate.h, accumulated-drift form)
+  const uint2* wl;
   const uint32_t* wl_cnt;
   float* marg;
+  const float* acc_dn;
 };
 
 // MODE 0: labels only (predict; every decided row's label written, queued
@@ -371,11 +376,15 @@ struct S1Args {
 // sum ||x - c||^2 with one exact per-cluster correction from the full sums
 // (k_update, sse_corr; DESIGN.md section 2 "Statistics and SSE").
 // GATED (MODE 1, no REV, no SSE, the batched re-score): every row the kernel
-// decides gets a fresh margin (km_s1_gate.h), every row it queues margin 0 (it
-// is screened again next time).  GATED 1: a wave screens only the rows of its
-// segment of the gate's work list, 16 entries per tile.  GATED 2: the dense
-// sweep with margins, for the passes that the host knows must screen every
-// row (no margins yet): no gate pass, no indirection.
+// decides gets a fresh margin, stored as a base against its new label's lower
+// total (km_s1_gate.h), every row it queues 0 (it is screened again next
+// time).  GATED 1: a wave screens only the rows of its segment of the gate's
+// work list, 16 entries per tile.  An entry carries the row and the label it
+// holds, and the tail bounds ||x|| from the sum of squares it needs for the
+// margin anyway, so a listed row costs its 4 DP bytes and no scattered 4-byte
+// read (labels, row norms).  GATED 2: the dense sweep with margins, for the
+// passes that the host knows must screen every row (no margins yet): no gate
+// pass, no indirection.
 template <int NS2, int NB, int MODE, bool REV = false, bool SSE = false, int GATED = 0>
 __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void k_s1(S1Args A) {
   if (*A.gate) return;  // a stopped batch (km_update_async): the rest of it is a no-op
@@ -470,22 +479,27 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
   // chain id bits of this lane's 8 accumulator positions (cb, i): chain 16 cb + 4 q + i
   const uint32_t qbits = (uint32_t)(4 * q) << MB;
 
-  struct Buf {
+  struct BufDense {
     float4 x[FQ / 4];
     float xn;
     int32_t old;
-    uint32_t row;  // LIST: the tile's row of this lane (>= n: none)
   };
+  struct BufList {
+    float4 x[FQ / 4];
+    uint2 ent;  // the tile's entry of this lane: {row (>= n: none), the label it holds}
+  };
+  using Buf = typename std::conditional<LIST, BufList, BufDense>::type;
   // LIST: this wave's work-list segment; the entry of the next tile to load
   // is fetched one load ahead of its row, so the two dependent loads of a
   // tile (entry, then row) never wait for each other in the loop
-  const uint32_t* wlp = nullptr;
-  uint32_t wln = 0, wnext = 0xFFFFFFFFu;
+  const uint2* wlp = nullptr;
+  uint32_t wln = 0;
+  uint2 wnext = make_uint2(0xFFFFFFFFu, 0u);
   const bool gscale = MARG && s1g_scale_ok(s);
   if constexpr (LIST) {
     wlp = A.wl + (size_t)gw * A.seg;
     wln = min(A.wl_cnt[gw], A.seg);
-    wnext = (uint32_t)c16 < wln ? wlp[c16] : 0xFFFFFFFFu;
+    if ((uint32_t)c16 < wln) wnext = wlp[c16];
   }
   // serpentine sweep (REV: its own instance, since a run-time select in the
   // row arithmetic cost the issue-bound c3 kernel 1.5%): step tiles mapped
@@ -495,10 +509,11 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
     uint32_t row;
     if constexpr (LIST) {
       // (tiles are loaded in order 0, 1, 2, ...: wnext is tile's entry)
-      row = wnext;
+      row = wnext.x;
+      B.ent = wnext;
       const uint32_t e = (tile + 1u) * 16u + (uint32_t)c16;
-      wnext = e < wln ? wlp[e] : 0xFFFFFFFFu;
-      B.row = row;
+      wnext = make_uint2(0xFFFFFFFFu, 0u);
+      if (e < wln) wnext = wlp[e];
     } else {
       row = tmap(tile) * 16u + (uint32_t)c16;
     }
@@ -506,8 +521,10 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
     const float4* xr = reinterpret_cast<const float4*>(A.X + (size_t)rr * DP + FQ * q);
 #pragma unroll
     for (int u = 0; u < FQ / 4; ++u) B.x[u] = xr[u];
-    B.xn = A.xnorm[rr];
-    if constexpr (MODE == 1) B.old = A.labels[rr];
+    if constexpr (!LIST) {
+      B.xn = A.xnorm[rr];
+      if constexpr (MODE == 1) B.old = A.labels[rr];
+    }
   };
 
   // fp32 re-score of candidates (slots sl[0..cnt-1], ascending key order)
@@ -678,9 +695,12 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
       if constexpr (MARG) {
         // a decided row: the winner against the other candidates (Lo) and
         // against everything above the threshold (the tile's bound from T);
-        // a queued one: 0
+        // a queued one: 0.  Every ring row is stored (the gate's invariant,
+        // k_s1_gate: a listed row never keeps its old base)
         if (act && q == 0)
-          A.marg[mt.x] = (kind == 0u && gscale) ? s1g_margin(fminf(lbo, sRl[wave * S1_RING + slot]), ubw) : 0.0f;
+          A.marg[mt.x] = (kind == 0u && gscale)
+                             ? s1g_base(s1g_margin(fminf(lbo, sRl[wave * S1_RING + slot]), ubw), A.acc_dn[lab1])
+                             : 0.0f;
       }
     } else {
       (void)nb;
@@ -690,7 +710,11 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
   // everything after the chains of one tile: certificate, labels, queue,
   // re-scoring ring
   auto tail = [&](uint32_t tile, const Buf& B, const float (&h)[2][4], float h2m) {
-    const uint32_t row = LIST ? B.row : tmap(tile) * 16u + (uint32_t)c16;
+    uint32_t row;
+    if constexpr (LIST)
+      row = B.ent.x;
+    else
+      row = tmap(tile) * 16u + (uint32_t)c16;
     const bool valid = row < n;
     // full slot ids in the heads, (chain << MB) | member: distinct keys, so
     // float comparisons order them totally (f32 denormals are kept, and +0
@@ -739,7 +763,26 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
     if (valid && q == 0) A.labels[row] = sPerm[f2u(la) & SLOTM] + (h2m < -1e30f ? 1 : 0);
     return;
 #endif
-    const float xn = B.xn;
+    // MARG: ||x||^2 in fp32 over the quad (the fresh margins' bounds); the list
+    // instance also takes its bound of ||x|| from it (no per-row norm read:
+    // NaN and inf rows still fail the `bad` test through it)
+    float xq = 0.0f;
+    if constexpr (MARG) {
+      float xs = 0.0f;
+#pragma unroll
+      for (int u = 0; u < FQ / 4; ++u) {
+        xs = fmaf(B.x[u].x, B.x[u].x, xs);
+        xs = fmaf(B.x[u].y, B.x[u].y, xs);
+        xs = fmaf(B.x[u].z, B.x[u].z, xs);
+        xs = fmaf(B.x[u].w, B.x[u].w, xs);
+      }
+      xq = quad_sum(xs);
+    }
+    float xn;
+    if constexpr (LIST)
+      xn = s1g_xnorm(xq);
+    else
+      xn = B.xn;
     const float E = fmaf(e1, xn, e0);
     const bool bad = !(m >= -3.0e38f && m <= 3.0e38f) || !(xn <= 3.0e38f);
     constexpr float RP = RHO * (1.0f + 2.0f * RHO);
@@ -769,7 +812,10 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
     // non-finite input: the full scan (kind 2)
     const bool dec1 = ok && cnt == 1u && labm >= 0;
     int32_t old = 0;
-    if constexpr (MODE == 1) old = (int32_t)min((uint32_t)B.old, (uint32_t)(A.k - 1));
+    if constexpr (LIST)
+      old = (int32_t)min(B.ent.y, (uint32_t)(A.k - 1));
+    else if constexpr (MODE == 1)
+      old = (int32_t)min((uint32_t)B.old, (uint32_t)(A.k - 1));
 #if KM_S1_ABL == 2
     // timing ablation (diagnostic builds only, wrong labels): no re-scoring
     emit(valid, row, dec1 || needy ? 0u : 2u, labm, 0, old);
@@ -777,18 +823,10 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
 #endif
     float lbT = 0.0f;  // MARG: lower bound of the distance to every centroid whose key is above T
     if constexpr (MARG) {
-      // fresh margins (km_s1_gate.h).  ||x||^2 in fp32 over the quad; the
-      // smallest key of any centroid but the argmin: the second smallest head
-      // or a chain's second key (distinct keys: the heads above m)
-      float xs = 0.0f;
-#pragma unroll
-      for (int u = 0; u < FQ / 4; ++u) {
-        xs = fmaf(B.x[u].x, B.x[u].x, xs);
-        xs = fmaf(B.x[u].y, B.x[u].y, xs);
-        xs = fmaf(B.x[u].z, B.x[u].z, xs);
-        xs = fmaf(B.x[u].w, B.x[u].w, xs);
-      }
-      const S1GRow gr = s1g_row(s, E, quad_sum(xs));
+      // fresh margins (km_s1_gate.h).  The smallest key of any centroid but
+      // the argmin: the second smallest head or a chain's second key (distinct
+      // keys: the heads above m)
+      const S1GRow gr = s1g_row(s, E, xq);
       float nl = h2m;
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb)
@@ -797,9 +835,12 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
       const float h2 = quad_min(nl);
       lbT = s1g_lb(T, RP, gr);
       // (rows with 2 .. LMAX candidates get theirs from the re-score; the
-      // rest of the undecided rows are queued: 0)
+      // rest of the undecided rows are queued: 0).  Invariant the gate relies
+      // on (k_s1_gate): every valid row of the tile is stored here or, being
+      // `needy`, in rescore -- exactly one of the two
       if (valid && !needy && q == 0)
-        A.marg[row] = (dec1 && gscale) ? s1g_margin(s1g_lb(h2, RP, gr), s1g_ub(m, RP, gr)) : 0.0f;
+        A.marg[row] =
+            (dec1 && gscale) ? s1g_base(s1g_margin(s1g_lb(h2, RP, gr), s1g_ub(m, RP, gr)), A.acc_dn[labm]) : 0.0f;
     }
     if constexpr (BATCH) {
       emit(valid && !needy, row, dec1 ? 0u : 2u, labm, 0, old);
@@ -1111,12 +1152,23 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
 // brought up to date (cref, a copy kept for this purpose alone, so that
 // whatever moved the centroids in between -- the update, a repair, new
 // centroids -- is covered), rounded up; then the largest shift, the second
-// largest and the largest one's index in shift[k .. k + 2]; cref = C.
+// largest and the largest one's index (all in LDS only); cref = C.
+// Then the clusters' running totals (km_s1_gate.h, accumulated-drift form):
+// acc[j] += shift[j] + the largest other shift, in float64 rounded up, and
+// their float images accud[j] >= acc[j] (the gate compares against it) and
+// accud[k + j] <= acc[j] (what a fresh margin is stored against).  `reset`
+// (the dense sweep follows and rewrites every margin) starts a new epoch,
+// acc = 0.  A non-finite shift does the same, except that this pass's upper
+// image is +inf: the gate lists every row, each listed row gets a new base
+// against the lower image 0, and the totals stay finite afterwards.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void k_s1_shift(const double* __restrict__ C, double* __restrict__ cref, int k,
-                                                   int d, float* __restrict__ shift, const int* __restrict__ gate) {
+                                                   int d, double* __restrict__ acc,
+                                                   float* __restrict__ accud, int reset,
+                                                   const int* __restrict__ gate) {
   if (*gate) return;
   __shared__ float sv[1024];
+  __shared__ float stop[3];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwv = blockDim.x >> 6;
   for (int j = wave; j < k; j += nwv) {
     double sh = 0.0;
@@ -1128,11 +1180,7 @@ __global__ __launch_bounds__(1024) void k_s1_shift(const double* __restrict__ C,
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) sh += __shfl_xor(sh, o);
-    if (lane == 0) {
-      const float v = s1g_shift(sh);
-      sv[j] = v;
-      shift[j] = v;
-    }
+    if (lane == 0) sv[j] = s1g_shift(sh);
   }
   __syncthreads();
   if (wave == 0) {
@@ -1155,73 +1203,154 @@ __global__ __launch_bounds__(1024) void k_s1_shift(const double* __restrict__ C,
       m1 = fmaxf(m1, om1);
     }
     if (lane == 0) {
-      shift[k] = m1;
-      shift[k + 1] = fmaxf(m2, 0.0f);  // (k = 1: no other centroid moves)
-      shift[k + 2] = __int_as_float(a1);
+      stop[0] = m1;
+      stop[1] = fmaxf(m2, 0.0f);  // (k = 1: no other centroid moves)
+      stop[2] = __int_as_float(a1);
+    }
+  }
+  __syncthreads();
+  {
+    const float top1 = stop[0], top2 = stop[1];
+    const int atop = __float_as_int(stop[2]);
+    for (int j = threadIdx.x; j < k; j += blockDim.x) {
+      float up, dn;
+      acc[j] = s1g_acc_pass(acc[j], sv[j], j == atop ? top2 : top1, top1, reset != 0, &up, &dn);
+      accud[j] = up;
+      accud[k + j] = dn;
     }
   }
 }
 
-// k_s1_gate: k_s1's grid; wave w owns rows [w seg, (w + 1) seg).  Per row the
-// margin takes one step (s1g_step) and is written back; a row whose margin is
-// not strictly positive (or not a number) is written 0 and appended to the
-// wave's segment of the work list -- ballot and popcount, in row order, one
-// count per wave, no atomics: the list, and so the order in which the change
-// list and the float64 sums see the rows, is the same on every run.  `init`
-// (no margins yet, or labels not k_s1's): every row is listed.
+// k_s1_gate: k_s1's grid; wave w owns rows [w seg, (w + 1) seg).  A pure read:
+// per row the label and the stored base (km_s1_gate.h, accumulated-drift
+// form); a row whose base is not strictly above its label's upper total (or
+// not a number) is appended, with its label, to the wave's segment of the work
+// list.  Nothing is written back -- so the list instance of k_s1 must store a
+// base (a fresh one, or 0) for EVERY row listed here, exactly once: a listed
+// row left as it was would keep a base that refers to its old label, or, after
+// a non-finite shift, to the old epoch's larger totals, and could pass the
+// test wrongly later.  (k_s1: the tail stores for every valid row that does
+// not go to the ring, `rescore` for every ring row, and the ring is flushed
+// at the end of the kernel.)  A lane takes 4 consecutive rows per 16-byte
+// load (a segment starts at a multiple of 16 rows), S1G_UNITS loads per array
+// and trip, and the next trip's loads are issued before this trip's rows are
+// sifted (two register sets, ping-pong): 4 to 8 KiB per wave, 48 to 96 KiB per
+// CU at twelve waves, stay in flight.  The list keeps row order -- a lane's
+// position is the wave prefix of the lanes' counts (three ballots of the
+// count's bits) -- with one count per wave and no atomics: the list, and so
+// the order in which the change list and the float64 sums see the rows, is the
+// same on every run.  `init` (labels not k_s1's, or a repair replaced
+// centroids): every row is listed; the bases are not read, the labels are,
+// since the entries carry them.
 struct S1GateArgs {
   const int32_t* labels;
-  float* marg;
+  const float* marg;
   int64_t n;
   int k;
   uint32_t seg;
-  const float* shift;  // [k + 3] (k_s1_shift)
-  uint32_t* wl;
+  const float* acc_up;  // [k] (k_s1_shift)
+  uint2* wl;
   uint32_t* wl_cnt;
   int init;
   const int32_t* init_dev;  // or nullptr: a device word that also asks for every row (a repair replaced centroids)
   const int* gate;
 };
 
+constexpr int S1G_UNITS = 2;                          // 16-byte loads per array, lane and trip
+constexpr uint32_t S1G_TRIP = 256u * S1G_UNITS;       // rows one wave takes per trip
+
 template <int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void k_s1_gate(S1GateArgs A) {
   if (*A.gate) return;
-  __shared__ float sSh[1024];
-  for (int i = threadIdx.x; i < A.k; i += WAVES * 64) sSh[i] = A.shift[i];
-  const float top1 = A.shift[A.k], top2 = A.shift[A.k + 1];
-  const uint32_t atop = (uint32_t)__float_as_int(A.shift[A.k + 2]);
+  __shared__ float sUp[1024];
+  for (int i = threadIdx.x; i < A.k; i += WAVES * 64) sUp[i] = A.acc_up[i];
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t gw = blockIdx.x * WAVES + wave;
   const uint64_t n = (uint64_t)A.n;
-  const uint64_t r0 = (uint64_t)gw * A.seg, r1 = min(n, r0 + A.seg);
-  uint32_t* wl = A.wl + (size_t)gw * A.seg;
+  const uint64_t r0 = (uint64_t)gw * A.seg, r1 = max(r0, min(n, r0 + A.seg));
+  uint2* wl = A.wl + (size_t)gw * A.seg;
   const uint64_t below = (1ull << lane) - 1ull;
   const bool init = A.init != 0 || (A.init_dev && *A.init_dev != 0);
+  const uint32_t km1 = (uint32_t)(A.k - 1);
   uint32_t cnt = 0;
-  constexpr int G = 4;  // chunks of 64 rows in flight
-  for (uint64_t base = r0; base < r1; base += 64 * G) {
-    int32_t lab[G];
-    float mg[G];
+  struct Trip {
+    int4 lab[S1G_UNITS];
+    float4 bs[S1G_UNITS];
+  };
+  // a full trip (every row of it below r1): 16-byte loads, aligned since
+  // r0 and the trip are multiples of 16 rows
+  auto fetch = [&](uint64_t base, Trip& T) {
 #pragma unroll
-    for (int u = 0; u < G; ++u) {
-      const uint64_t row = base + 64 * u + lane;
-      const bool in = row < r1;
-      lab[u] = (in && !init) ? A.labels[row] : 0;
-      mg[u] = (in && !init) ? A.marg[row] : 0.0f;
+    for (int u = 0; u < S1G_UNITS; ++u) {
+      const uint64_t row = base + 256u * u + 4u * (uint32_t)lane;
+      T.lab[u] = *reinterpret_cast<const int4*>(A.labels + row);
+      T.bs[u] = init ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : *reinterpret_cast<const float4*>(A.marg + row);
     }
+  };
+  // the segment's last, partial trip: element by element, nothing past r1
+  auto fetch_tail = [&](uint64_t base, Trip& T) {
 #pragma unroll
-    for (int u = 0; u < G; ++u) {
-      const uint64_t row = base + 64 * u + lane;
-      const bool in = row < r1;
-      const uint32_t l = min((uint32_t)lab[u], (uint32_t)(A.k - 1));
-      const float m2 = s1g_step(mg[u], sSh[l], l == atop ? top2 : top1);
-      const bool keep = !init && m2 > 0.0f;
-      if (in) A.marg[row] = keep ? m2 : 0.0f;
-      const uint64_t mask = __ballot(in && !keep);
-      if (in && !keep) wl[cnt + (uint32_t)__popcll(mask & below)] = (uint32_t)row;
-      cnt += (uint32_t)__popcll(mask);
+    for (int u = 0; u < S1G_UNITS; ++u) {
+      const uint64_t row = base + 256u * u + 4u * (uint32_t)lane;
+      int32_t l[4];
+      float b[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const bool in = row + i < r1;
+        l[i] = in ? A.labels[row + i] : 0;
+        b[i] = (in && !init) ? A.marg[row + i] : 0.0f;
+      }
+      T.lab[u] = make_int4(l[0], l[1], l[2], l[3]);
+      T.bs[u] = make_float4(b[0], b[1], b[2], b[3]);
     }
+  };
+  auto sift = [&](uint64_t base, const Trip& T) {
+#pragma unroll
+    for (int u = 0; u < S1G_UNITS; ++u) {
+      const uint64_t row = base + 256u * u + 4u * (uint32_t)lane;
+      // (clamped as k_s1's tail clamps the label it reads)
+      auto clampk = [&](int32_t v) -> uint32_t { return (uint32_t)v < km1 ? (uint32_t)v : km1; };
+      const uint32_t l[4] = {clampk(T.lab[u].x), clampk(T.lab[u].y), clampk(T.lab[u].z), clampk(T.lab[u].w)};
+      const float b[4] = {T.bs[u].x, T.bs[u].y, T.bs[u].z, T.bs[u].w};
+      bool ls[4];
+      uint32_t c = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        ls[i] = row + i < r1 && (init || !s1g_keep(b[i], sUp[l[i]]));
+        c += ls[i] ? 1u : 0u;
+      }
+      const uint64_t b0 = __ballot((c & 1u) != 0u), b1 = __ballot((c & 2u) != 0u), b2 = __ballot((c & 4u) != 0u);
+      if ((b0 | b1 | b2) == 0ull) continue;
+      uint32_t pos = cnt + (uint32_t)__popcll(b0 & below) + 2u * (uint32_t)__popcll(b1 & below) +
+                     4u * (uint32_t)__popcll(b2 & below);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (ls[i]) wl[pos++] = make_uint2((uint32_t)(row + i), l[i]);
+      cnt += (uint32_t)__popcll(b0) + 2u * (uint32_t)__popcll(b1) + 4u * (uint32_t)__popcll(b2);
+    }
+  };
+  const uint64_t rfull = r0 + (r1 - r0) / S1G_TRIP * S1G_TRIP;  // the end of the full trips
+  uint64_t base = r0;
+  if (base < rfull) {
+    Trip ta, tb;
+    fetch(base, ta);
+    tb = ta;
+    for (;;) {
+      if (base + S1G_TRIP < rfull) fetch(base + S1G_TRIP, tb);
+      sift(base, ta);
+      base += S1G_TRIP;
+      if (base >= rfull) break;
+      if (base + S1G_TRIP < rfull) fetch(base + S1G_TRIP, ta);
+      sift(base, tb);
+      base += S1G_TRIP;
+      if (base >= rfull) break;
+    }
+  }
+  if (base < r1) {
+    Trip tt;
+    fetch_tail(base, tt);
+    sift(base, tt);
   }
   if (lane == 0) A.wl_cnt[gw] = cnt;
 }
@@ -1554,11 +1683,12 @@ hipError_t launch_s1_gate(const Geometry& g, const double* C64, const int32_t* l
   int nbk;
   uint32_t seg;
   (void)s1_grid(g, n_cu, &nbk, &seg);
-  hipLaunchKernelGGL(k_s1_shift, dim3(1), dim3(1024), 0, s, C64, b.cref, g.k, g.d, b.shift, gate);
+  hipLaunchKernelGGL(k_s1_shift, dim3(1), dim3(1024), 0, s, C64, b.cref, g.k, g.d, b.acc, b.accud,
+                     init == 2 ? 1 : 0, gate);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (init == 2) return hipSuccess;  // the dense sweep with margins follows: no list
-  S1GateArgs a{labels, b.marg, g.n, g.k, seg, b.shift, b.wl, b.wl_cnt, init, init_dev, gate};
+  S1GateArgs a{labels, b.marg, g.n, g.k, seg, b.accud, b.wl, b.wl_cnt, init, init_dev, gate};
   if (s1_geo_waves(g) == 12)
     hipLaunchKernelGGL(k_s1_gate<12>, dim3(nbk), dim3(12 * 64), 0, s, a);
   else
@@ -1583,7 +1713,8 @@ hipError_t launch_s1(const float* X, const float* xnorm, const Geometry& g, cons
   ql->nwaves = (uint32_t)nw;
   if (sse && !delta) return hipErrorInvalidValue;  // residuals ride with delta statistics only
   S1Args a{X, xnorm, g.n, g.k, g.d, seg, img, cn2o, cft, perm, cst, labels, queue, qcount, chg, chg_cnt, sse, gate,
-           gt ? gt->wl : nullptr, gt ? gt->wl_cnt : nullptr, gt ? gt->marg : nullptr};
+           gt ? gt->wl : nullptr, gt ? gt->wl_cnt : nullptr, gt ? gt->marg : nullptr,
+           gt ? gt->accud + g.k : nullptr};
   if (gt && (!delta || sse || !s1_gate_ok(g))) return hipErrorInvalidValue;
   const size_t lds = s1_lds_bytes(sg.ns2, sg.nb, !s1_table_global(sg.ns2, sg.nb));
   if (lds > 160 * 1024) return hipErrorInvalidValue;
