@@ -24,9 +24,9 @@ KM_ABI_VERSION = 6
 KM_OK = 0
 KM_EMPTY = 1
 
-KM_K_ASSIGN, KM_K_RESOLVE, KM_K_STATS, KM_K_UPDATE, KM_K_PREP = range(5)
+KM_K_ASSIGN, KM_K_RESOLVE, KM_K_STATS, KM_K_UPDATE, KM_K_PREP, KM_K_SEED = range(6)
 KERNEL_KINDS = {"assign": KM_K_ASSIGN, "resolve": KM_K_RESOLVE, "stats": KM_K_STATS, "update": KM_K_UPDATE,
-                "prep": KM_K_PREP}
+                "prep": KM_K_PREP, "seed": KM_K_SEED}
 
 
 KM_STOP_CONVERGED, KM_STOP_EMPTY, KM_STOP_NONFINITE = 1, 2, 3
@@ -92,6 +92,12 @@ SIGNATURES = {
     "km_gather_rows": [_P, _PI64, _I32, _PD],
     "km_bernoulli_sample": [_P, ctypes.POINTER(ctypes.c_uint64), _PI64, _PI64, _I32, ctypes.c_double, _PI64,
                             ctypes.c_int64, _PI64],
+    "km_seed_begin": [_P],
+    "km_seed_update": [_P, _I32, _PD],
+    "km_seed_sample": [_P, ctypes.c_uint64, _I32, _I64, _D, _D, _PI64, _I64, _PI64],
+    "km_seed_weights": [_P, _I32, _PI64],
+    "km_seed_read": [_P, _PD, _PI32],
+    "km_seed_end": [_P],
     "km_predict": [_P, _PI32],
     "km_labels": [_P, _PI32],
     "km_profile": [_P, _I32],

@@ -286,4 +286,39 @@ hipError_t launch_s1_apply(double* stats, double* full, int64_t len, int mode, c
 hipError_t launch_gen_blobs(float* X, const Geometry& g, int64_t row_offset, int32_t n_centers, float box,
                             float stddev, uint64_t seed, hipStream_t s);
 
+// counter-based hash of k_gen_blobs and of the k-means|| pick rule
+__host__ __device__ inline uint64_t splitmix64(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
+// ---- k-means|| seeding (km_seed.hip; km_seed_* of kmeans_amd.h) -------------
+// per-row state: D2 (float64 squared distance to the nearest candidate so
+// far) and near (that candidate's id)
+hipError_t launch_seed_init(double* D2, int32_t* near, int64_t n, hipStream_t s);
+// workgroups of the fold / of the pick passes for n rows (sizes of the
+// partial-sum and count buffers; they depend on n and the device only, so
+// the summation order of phi is fixed)
+int seed_fold_blocks(int64_t n, int n_cu);
+int seed_sample_blocks(int64_t n, int n_cu);
+// the exact float64 squared distance of every row to centroid labels[row] of
+// C64 [k][d] (NumPy's pairwise order, km_exact.h), min-folded into D2 / near
+// (strict <: the earliest candidate keeps ties, a NaN never replaces a
+// value); part[b] = workgroup b's sum of the new D2, part[blocks] = their sum
+// in workgroup order (no floating-point atomics: bit-identical on a repeat)
+hipError_t launch_seed_fold(const float* X, const Geometry& g, const double* C64, const int32_t* labels,
+                            int32_t first_id, double* D2, int32_t* near, double* part, int n_cu, hipStream_t s);
+// rows with u * phi < ell * D2[i], u the 53-bit hash of (seed, round, row0 +
+// i): local indices ascending into out[0..cap) (never past cap);
+// offs[blocks] = the number of picks (possibly > cap: the caller checks).
+// cnt: blocks words, offs: blocks + 1
+hipError_t launch_seed_sample(const double* D2, int64_t n, uint64_t seed, int32_t round, int64_t row0, double ell,
+                              double phi, uint32_t* cnt, int64_t* offs, int64_t* out, int64_t cap, int n_cu,
+                              hipStream_t s);
+// counts[j] += rows with near == j, j < m_total (counts zeroed by the caller)
+hipError_t launch_seed_weights(const int32_t* near, int64_t n, int32_t m_total, unsigned long long* counts, int n_cu,
+                               hipStream_t s);
+
 }  // namespace km

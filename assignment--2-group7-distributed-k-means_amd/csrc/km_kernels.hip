@@ -4910,13 +4910,7 @@ hipError_t launch_gather_rows(const float* X, const Geometry& g, const int64_t* 
 // Synthetic Gaussian blobs, counter-based so that a row's
 // value depends only on (seed, global row, feature): shard-invariant.
 // ---------------------------------------------------------------------------
-__host__ __device__ inline uint64_t splitmix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
+// (splitmix64: km_internal.h, shared with the seeding hash of km_seed.hip)
 __global__ void k_gen_blobs(float* __restrict__ X, int64_t n, int d, int dp, int64_t row_offset, int n_centers,
                             float box, float stddev, uint64_t seed) {
   const int64_t tot = n * dp;

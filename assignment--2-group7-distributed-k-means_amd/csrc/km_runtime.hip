@@ -216,6 +216,16 @@ struct km_ctx {
   bool rep_wait = false;          // mode 2: km_update_async left the iteration to km_repair_apply_async
   double rep_tol = 0.0;
   bool rep_fold = false;
+  // k-means|| seeding state of the local rows (km_seed_begin .. km_seed_end),
+  // independent of the Lloyd state above
+  bool seed_on = false;
+  double* seed_d2 = nullptr;      // [n] squared distance to the nearest candidate so far
+  int32_t* seed_near = nullptr;   // [n] that candidate's id
+  double* seed_part = nullptr;    // the fold's workgroup sums of D2, then phi
+  uint32_t* seed_cnt = nullptr;   // pick pass: picks per workgroup
+  int64_t* seed_offs = nullptr;   // ... their exclusive scan, then the total
+  int64_t* seed_out = nullptr;    // ... the picks (seed_out_cap slots)
+  int64_t seed_out_cap = 0;
   // staging
   float* pinned = nullptr;      // two staging halves of pinned_floats each
   size_t pinned_floats = 0;
@@ -339,7 +349,19 @@ void free_centroids(km_ctx* c) {
   c->have_c = false;
 }
 
+void free_seed(km_ctx* c) {
+  dfree(c->seed_d2);
+  dfree(c->seed_near);
+  dfree(c->seed_part);
+  dfree(c->seed_cnt);
+  dfree(c->seed_offs);
+  dfree(c->seed_out);
+  c->seed_out_cap = 0;
+  c->seed_on = false;
+}
+
 void free_data(km_ctx* c) {
+  free_seed(c);  // the state describes the rows being released
   dfree(c->X);
   dfree(c->labels);
   dfree(c->queue);
@@ -1666,6 +1688,124 @@ int km_labels(km_ctx* c, int32_t* labels_out) {
   if (c->g.n > 0)
     KM_HIP(hipMemcpyAsync(labels_out, c->labels, sizeof(int32_t) * c->g.n, hipMemcpyDeviceToHost, c->stream));
   KM_HIP(hipStreamSynchronize(c->stream));
+  return KM_OK;
+}
+
+// ---- k-means|| seeding (seeding.py states the algorithm) --------------------
+int km_seed_begin(km_ctx* c) {
+  KM_REQUIRE(c, KM_ERR_ARG, "null ctx");
+  KM_REQUIRE(c->loaded, KM_ERR_STATE, "km_seed_begin: load data first");
+  KM_HIP(hipSetDevice(c->device));
+  free_seed(c);
+  const int64_t rows = std::max<int64_t>(c->g.n, 1);
+  const int nbf = km::seed_fold_blocks(c->g.n, c->n_cu), nbs = km::seed_sample_blocks(c->g.n, c->n_cu);
+  KM_HIP(hipMalloc(&c->seed_d2, sizeof(double) * rows));
+  KM_HIP(hipMalloc(&c->seed_near, sizeof(int32_t) * rows));
+  KM_HIP(hipMalloc(&c->seed_part, sizeof(double) * (nbf + 1)));
+  KM_HIP(hipMalloc(&c->seed_cnt, sizeof(uint32_t) * nbs));
+  KM_HIP(hipMalloc(&c->seed_offs, sizeof(int64_t) * (nbs + 1)));
+  KM_HIP(km::launch_seed_init(c->seed_d2, c->seed_near, c->g.n, c->stream));
+  KM_HIP(hipStreamSynchronize(c->stream));
+  c->seed_on = true;
+  return KM_OK;
+}
+
+int km_seed_update(km_ctx* c, int32_t first_id, double* phi_local) {
+  KM_REQUIRE(c && phi_local, KM_ERR_ARG, "km_seed_update: null arg");
+  KM_REQUIRE(c->loaded && c->seed_on, KM_ERR_STATE, "km_seed_update: call km_seed_begin first");
+  KM_REQUIRE(c->have_c, KM_ERR_STATE, "km_seed_update: set the candidate batch with km_set_centroids first");
+  KM_REQUIRE(c->path != 0, KM_ERR_UNSUPPORTED, "km_seed_update: unsupported geometry");
+  KM_REQUIRE(first_id >= 0, KM_ERR_ARG, "km_seed_update: negative first_id");
+  *phi_local = 0.0;
+  KM_HIP(hipSetDevice(c->device));
+  {
+    const int rcf = flush_assign(c);
+    if (rcf != KM_OK) return rcf;
+  }
+  // the labels-only assignment of km_predict: nearest of the batch, exactly
+  if (c->g.n > 0) {
+    const int rc = run_assign(c, false);
+    if (rc != KM_OK) return rc;
+  }
+  c->delta_ready = false;  // the labels are the batch's, not the sums' assignment
+  {
+    ProfScope ps(c, KM_K_SEED, true);
+    KM_HIP(km::launch_seed_fold(c->X, c->g, c->C64_cur, c->labels, first_id, c->seed_d2, c->seed_near, c->seed_part,
+                                c->n_cu, c->stream));
+  }
+  const int nbf = km::seed_fold_blocks(c->g.n, c->n_cu);
+  KM_HIP(hipMemcpyAsync(phi_local, c->seed_part + nbf, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  KM_HIP(hipStreamSynchronize(c->stream));
+  return KM_OK;
+}
+
+int km_seed_sample(km_ctx* c, uint64_t seed, int32_t round, int64_t global_row0, double ell, double phi, int64_t* out,
+                   int64_t cap, int64_t* n_out) {
+  KM_REQUIRE(c && n_out, KM_ERR_ARG, "km_seed_sample: null arg");
+  *n_out = 0;
+  KM_REQUIRE(c->loaded && c->seed_on, KM_ERR_STATE, "km_seed_sample: call km_seed_begin first");
+  KM_REQUIRE(cap >= 0 && (cap == 0 || out), KM_ERR_ARG, "km_seed_sample: null out");
+  KM_REQUIRE(global_row0 >= 0, KM_ERR_ARG, "km_seed_sample: negative global_row0");
+  if (c->g.n == 0) return KM_OK;
+  KM_HIP(hipSetDevice(c->device));
+  if (cap > c->seed_out_cap || !c->seed_out) {
+    KM_HIP(hipStreamSynchronize(c->stream));
+    dfree(c->seed_out);
+    c->seed_out_cap = 0;
+    KM_HIP(hipMalloc(&c->seed_out, sizeof(int64_t) * std::max<int64_t>(cap, 1)));
+    c->seed_out_cap = std::max<int64_t>(cap, 1);
+  }
+  KM_HIP(km::launch_seed_sample(c->seed_d2, c->g.n, seed, round, global_row0, ell, phi, c->seed_cnt, c->seed_offs,
+                                c->seed_out, cap, c->n_cu, c->stream));
+  const int nbs = km::seed_sample_blocks(c->g.n, c->n_cu);
+  int64_t total = 0;
+  KM_HIP(hipMemcpyAsync(&total, c->seed_offs + nbs, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+  KM_HIP(hipStreamSynchronize(c->stream));
+  *n_out = total;
+  KM_REQUIRE(total <= cap, KM_ERR_ARG, "km_seed_sample: more picks than the output holds");
+  if (total > 0) {
+    KM_HIP(hipMemcpyAsync(out, c->seed_out, sizeof(int64_t) * total, hipMemcpyDeviceToHost, c->stream));
+    KM_HIP(hipStreamSynchronize(c->stream));
+  }
+  return KM_OK;
+}
+
+int km_seed_weights(km_ctx* c, int32_t m_total, int64_t* counts_out) {
+  KM_REQUIRE(c && counts_out, KM_ERR_ARG, "km_seed_weights: null arg");
+  KM_REQUIRE(c->loaded && c->seed_on, KM_ERR_STATE, "km_seed_weights: call km_seed_begin first");
+  KM_REQUIRE(m_total > 0, KM_ERR_ARG, "km_seed_weights: m_total must be positive");
+  KM_HIP(hipSetDevice(c->device));
+  unsigned long long* dcounts = nullptr;
+  KM_HIP(hipMalloc(&dcounts, sizeof(unsigned long long) * (size_t)m_total));
+  hipError_t e = hipMemsetAsync(dcounts, 0, sizeof(unsigned long long) * (size_t)m_total, c->stream);
+  if (e == hipSuccess) e = km::launch_seed_weights(c->seed_near, c->g.n, m_total, dcounts, c->n_cu, c->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(counts_out, dcounts, sizeof(int64_t) * (size_t)m_total, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(dcounts);
+  if (e != hipSuccess) return fail(KM_ERR_HIP, std::string("km_seed_weights: ") + hipGetErrorString(e));
+  return KM_OK;
+}
+
+int km_seed_read(km_ctx* c, double* d2_out, int32_t* near_out) {
+  KM_REQUIRE(c, KM_ERR_ARG, "null ctx");
+  KM_REQUIRE(c->loaded && c->seed_on, KM_ERR_STATE, "km_seed_read: call km_seed_begin first");
+  if (c->g.n == 0) return KM_OK;
+  KM_HIP(hipSetDevice(c->device));
+  if (d2_out)
+    KM_HIP(hipMemcpyAsync(d2_out, c->seed_d2, sizeof(double) * c->g.n, hipMemcpyDeviceToHost, c->stream));
+  if (near_out)
+    KM_HIP(hipMemcpyAsync(near_out, c->seed_near, sizeof(int32_t) * c->g.n, hipMemcpyDeviceToHost, c->stream));
+  KM_HIP(hipStreamSynchronize(c->stream));
+  return KM_OK;
+}
+
+int km_seed_end(km_ctx* c) {
+  KM_REQUIRE(c, KM_ERR_ARG, "null ctx");
+  KM_REQUIRE(c->seed_on, KM_ERR_STATE, "km_seed_end: call km_seed_begin first");
+  KM_HIP(hipSetDevice(c->device));
+  KM_HIP(hipStreamSynchronize(c->stream));
+  free_seed(c);
   return KM_OK;
 }
 

@@ -266,6 +266,49 @@ class HipEngine:
         self._c(rc, "km_bernoulli_sample")
         return out[:n.value].copy()
 
+    # -- k-means|| seeding (km_seed_*; seeding.py drives these) -------------------
+    def seed_begin(self) -> None:
+        """Per-row seeding state in HBM: D2 = +inf, near = -1 (12 B per row)."""
+        self._c(self.lib.km_seed_begin(self.ctx), "km_seed_begin")
+
+    def seed_update(self, first_id: int) -> float:
+        """Fold the current centroids (a batch of new candidates with ids from
+        ``first_id``) into D2 / near; this rank's sum of D2."""
+        phi = ctypes.c_double(0.0)
+        self._c(self.lib.km_seed_update(self.ctx, int(first_id), ctypes.byref(phi)), "km_seed_update")
+        return phi.value
+
+    def seed_sample(self, seed: int, rnd: int, global_row0: int, ell: float, phi: float,
+                    cap: Optional[int] = None) -> Optional[np.ndarray]:
+        """The round's picks among the local rows (local indices, ascending),
+        or None when they exceed ``cap`` (default 4 ell + 64): the caller then
+        applies the rule to ``seed_read``'s D2 on the host."""
+        cap = int(4.0 * ell) + 64 if cap is None else int(cap)
+        out = np.empty(max(cap, 1), dtype=np.int64)
+        n = ctypes.c_int64(0)
+        rc = self.lib.km_seed_sample(self.ctx, ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), int(rnd), int(global_row0),
+                                     float(ell), float(phi), _ptr(out, _PI64), cap, ctypes.byref(n))
+        if rc == -1:  # KM_ERR_ARG: more picks than cap
+            return None
+        self._c(rc, "km_seed_sample")
+        return out[:n.value].copy()
+
+    def seed_weights(self, m_total: int) -> np.ndarray:
+        """Local rows per nearest candidate id (int64 [m_total])."""
+        out = np.zeros(int(m_total), dtype=np.int64)
+        self._c(self.lib.km_seed_weights(self.ctx, int(m_total), _ptr(out, _PI64)), "km_seed_weights")
+        return out
+
+    def seed_read(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(D2 float64 [n], near int32 [n]) of the local rows."""
+        d2 = np.empty(self.n, dtype=np.float64)
+        near = np.empty(self.n, dtype=np.int32)
+        self._c(self.lib.km_seed_read(self.ctx, _ptr(d2, _PD), _ptr(near, _PI32)), "km_seed_read")
+        return d2, near
+
+    def seed_end(self) -> None:
+        self._c(self.lib.km_seed_end(self.ctx), "km_seed_end")
+
     def predict(self) -> np.ndarray:
         out = np.empty(self.n, dtype=np.int32)
         self._c(self.lib.km_predict(self.ctx, _ptr(out, _PI32)), "km_predict")
@@ -294,7 +337,7 @@ class HipEngine:
         return out
 
     # -- profiling ---------------------------------------------------------------
-    _PHASES = {"assign": 0, "resolve": 1, "stats": 2, "update": 3, "prep": 4}   # KM_K_* (kmeans_amd.h)
+    _PHASES = {"assign": 0, "resolve": 1, "stats": 2, "update": 3, "prep": 4, "seed": 5}   # KM_K_* (kmeans_amd.h)
 
     def profile(self, enable: bool = True, phases=None, every: int = 1) -> None:
         """Time launches with HIP events: every phase, or only ``phases``

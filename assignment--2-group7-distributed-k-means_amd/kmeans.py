@@ -25,7 +25,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from . import _lib, sampling
+from . import _lib, sampling, seeding
 from .comm import Communicator
 from .dataset import DeviceBlobs, EmptyDataset, LocalRDD, Placement, place
 from .engine import make_engine
@@ -325,6 +325,10 @@ class KMeans:
 
     Parameters: k, max_iter, tolerance (max centroid shift), seed (sampling of
     the initial centroids), compute_sse (track the SSE each iteration).
+    Keyword-only, beyond the reference: init ("random": the reference's
+    takeSample of k rows, the default; "k-means||": seeding.py), init_rounds
+    (rounds of k-means||), oversampling (its expected picks per round, ell;
+    None = 2 k).
 
     Compute contract: rows are stored in HBM as float32, rounded once at load
     (a float64 input is not copied at full precision); every row the fit uses
@@ -340,12 +344,17 @@ class KMeans:
     _engine_factory = None  # test seam: tests/ inject a CPU engine for host-logic tests
 
     def __init__(self, k: int = 3, max_iter: int = 100, tolerance: float = 1e-4,
-                 seed: int = 42, compute_sse: bool = False):
+                 seed: int = 42, compute_sse: bool = False, *, init: str = "random", init_rounds: int = 5,
+                 oversampling: Optional[float] = None):
         self.k = k
         self.max_iter = max_iter
         self.tolerance = tolerance
         self.seed = seed
         self.compute_sse = compute_sse
+        self.init = init
+        self.init_rounds = init_rounds
+        self.oversampling = oversampling
+        self._init_info = None  # k-means||: rounds run and candidates of the last fit
         self.centroids: np.ndarray = None
         self.sse_history: List[float] = []
         self._validate_parameters()
@@ -361,6 +370,12 @@ class KMeans:
             raise ValueError(f"max_iter must be positive, got {self.max_iter}")
         if self.tolerance <= 0:
             raise ValueError(f"tolerance must be positive, got {self.tolerance}")
+        if self.init not in ("random", "k-means||"):
+            raise ValueError(f"init must be 'random' or 'k-means||', got {self.init!r}")
+        if self.init_rounds < 1:
+            raise ValueError(f"init_rounds must be at least 1, got {self.init_rounds}")
+        if self.oversampling is not None and not self.oversampling > 0:
+            raise ValueError(f"oversampling must be positive, got {self.oversampling}")
 
     # -- hooks -----------------------------------------------------------------------
     def _empty_seed(self) -> int:
@@ -385,7 +400,13 @@ class KMeans:
         return run
 
     def _initialize_centroids(self, run: LloydRunner) -> np.ndarray:
-        """kmeans_spark.py:58-82: k distinct rows by the takeSample policy."""
+        """kmeans_spark.py:58-82: k distinct rows by the takeSample policy
+        (init="random"), or k-means|| seeding (seeding.py)."""
+        self._init_info = None
+        if self.init == "k-means||":
+            centroids, self._init_info = seeding.kmeans_parallel(run, self.k, self.seed, self.init_rounds,
+                                                                 self.oversampling)
+            return centroids
         gidx = sampling.take_sample(run.pl.global_sizes, self.k, self.seed, run.comm, run.sampler)
         if len(gidx) < self.k:
             raise ValueError(f"Not enough data points ({len(gidx)}) to initialize {self.k} clusters")
@@ -411,6 +432,9 @@ class KMeans:
         if say:
             say(f"Starting K-Means with k={self.k}, max_iter={self.max_iter}, tolerance={self.tolerance}")
             say(f"SSE computation: {'ENABLED' if self.compute_sse else 'DISABLED (for performance)'}")
+            if self._init_info is not None:
+                say(f"Initialization: k-means|| (rounds={self._init_info['rounds']}, "
+                    f"candidates={self._init_info['candidates']})")
         out_dtype = run.pl.dtype
         run.engine.set_centroids(np.asarray(self.centroids, dtype=np.float64))
         run.engine.set_sse(self.compute_sse)

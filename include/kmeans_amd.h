@@ -86,7 +86,8 @@ typedef struct km_info {
 #define KM_K_STATS 2
 #define KM_K_UPDATE 3
 #define KM_K_PREP 4
-#define KM_K_COUNT 5
+#define KM_K_SEED 5 /* k_seed_fold of km_seed_update (added within ABI 6) */
+#define KM_K_COUNT 6
 
 int km_abi_version(void);
 const char* km_last_error(void);
@@ -240,6 +241,47 @@ int km_bernoulli_sample(km_ctx* ctx, const uint64_t* seeds, const int64_t* sizes
 int km_predict(km_ctx* ctx, int32_t* labels_out);
 /* Labels of the last km_assign_stats (device -> host). */
 int km_labels(km_ctx* ctx, int32_t* labels_out);
+
+/* k-means|| seeding (Bahmani et al. 2012): an initialisation the reference
+ * does not have (its only one is takeSample, kmeans_spark.py:58-82); the
+ * algorithm is stated in seeding.py.  The passes over the local rows run
+ * here, the round loop and the weighted recluster of the candidates on the
+ * host.  (Added within ABI 6: new entry points, no existing layout changes.)
+ * Every call returns KM_ERR_STATE before km_load_begin, and every call but
+ * km_seed_begin before km_seed_begin.  A context with 0 rows is valid (phi 0,
+ * no picks, zero counts).  The state is independent of the Lloyd state: it
+ * survives km_set_centroids and is released by km_seed_end, km_load_begin,
+ * km_generate_blobs and km_destroy.
+ *
+ * km_seed_begin: per local row, D2 (float64, the squared distance to the
+ * nearest candidate so far; starts at +inf) and near (int32, that candidate's
+ * id; starts at -1): 12 bytes per row. */
+int km_seed_begin(km_ctx* ctx);
+/* Fold a batch of m new candidates, the current centroids (km_set_centroids
+ * with k = m), ids first_id .. first_id + m - 1, into the state.  Per row:
+ * j = np.argmin(np.linalg.norm(C - x, axis=1)) by the labels-only assignment
+ * of km_predict (the context is left as after km_predict(ctx, NULL); delta
+ * statistics are invalidated); t = np.add.reduce((C[j] - x) * (C[j] - x)) in
+ * float64, NumPy's pairwise order, no fused multiply-add; if t < D2 then
+ * D2 = t, near = first_id + j (the earliest candidate keeps ties, a NaN never
+ * replaces a value).  *phi_local = the sum of D2 over the local rows, in a
+ * fixed order (bit-identical between identical calls).  Synchronises. */
+int km_seed_update(km_ctx* ctx, int32_t first_id, double* phi_local);
+/* The pick rule of one round over the local rows: row i (global index
+ * g = global_row0 + i) is picked iff u * phi < ell * D2[i], both products
+ * rounded in float64, u = (h >> 11) * 2^-53,
+ * h = splitmix64(splitmix64(seed ^ (round * 0xD1B54A32D192ED03 mod 2^64)) ^ g).
+ * out[0..*n_out): local indices, ascending.  KM_ERR_ARG when the picks exceed
+ * cap (*n_out = their number; out is not written): the caller then applies
+ * the rule itself to km_seed_read's D2. */
+int km_seed_sample(km_ctx* ctx, uint64_t seed, int32_t round, int64_t global_row0, double ell, double phi,
+                   int64_t* out, int64_t cap, int64_t* n_out);
+/* counts_out[j] = local rows with near == j, j < m_total. */
+int km_seed_weights(km_ctx* ctx, int32_t m_total, int64_t* counts_out);
+/* The state to the host (d2_out[n], near_out[n]); either may be NULL. */
+int km_seed_read(km_ctx* ctx, double* d2_out, int32_t* near_out);
+/* Release the state. */
+int km_seed_end(km_ctx* ctx);
 
 /* Screening kernel.  A cost choice: labels, sums and SSE are exact in every
  * mode.  -1 (default): the one-MFMA screen k_s1 (mode 4) wherever the
