@@ -128,11 +128,26 @@ constexpr bool s1_table_global(int ns2, int nb) { return s1_lds_bytes(ns2, nb, t
 #ifndef KM_S1_GATE
 #define KM_S1_GATE 1
 #endif
-constexpr size_t s1_gate_lds(int ns2, int nb) { return (size_t)s1_waves(ns2, nb) * s1_ring(ns2, nb) * 4; }
-constexpr bool s1_gated(int ns2, int nb) {
+// (and the clusters' lower totals, one float per padded cluster: the tail and
+// the re-score read them from LDS, not from memory, so neither waits on a
+// global load that would drain the row loads in flight behind it)
+constexpr size_t s1_gate_ring_lds(int ns2, int nb) { return (size_t)s1_waves(ns2, nb) * s1_ring(ns2, nb) * 4; }
+constexpr size_t s1_gate_lds(int ns2, int nb) { return s1_gate_ring_lds(ns2, nb) + (size_t)32 * nb * 4; }
+constexpr bool s1_gated_with(int ns2, int nb, size_t extra) {
   return KM_S1_GATE && s1_batched(ns2) && s1_tiles(ns2) == 1 && !s1_table_global(ns2, nb) &&
-         s1_lds_bytes(ns2, nb, true) + s1_gate_lds(ns2, nb) <= 160 * 1024;
+         s1_lds_bytes(ns2, nb, true) + extra <= 160 * 1024;
 }
+constexpr bool s1_gated(int ns2, int nb) { return s1_gated_with(ns2, nb, s1_gate_lds(ns2, nb)); }
+// the totals' table took no geometry out of the gate (s1_gate_ok's list): each
+// is gated exactly when it was with the ring floats alone
+constexpr bool s1_gated_kept(int ns2, int nb) {
+  return s1_gated(ns2, nb) == s1_gated_with(ns2, nb, s1_gate_ring_lds(ns2, nb));
+}
+static_assert(s1_gated_kept(2, 2) && s1_gated_kept(2, 4) && s1_gated_kept(2, 6) && s1_gated_kept(2, 8) &&
+                  s1_gated_kept(1, 2) && s1_gated_kept(1, 4) && s1_gated_kept(1, 6) && s1_gated_kept(1, 8) &&
+                  s1_gated_kept(1, 12) && s1_gated_kept(1, 16),
+              "the lower totals' LDS table must not cost a geometry its gate");
+static_assert(!KM_S1_GATE || !KM_S1_W12 || s1_gated(2, 8), "the c3 geometry is gated");
 
 
 __device__ __forceinline__ uint32_t f2u(float v) { return __float_as_uint(v); }
@@ -382,9 +397,19 @@ struct S1Args {
 // work list, 16 entries per tile.  An entry carries the row and the label it
 // holds, and the tail bounds ||x|| from the sum of squares it needs for the
 // margin anyway, so a listed row costs its 4 DP bytes and no scattered 4-byte
-// read (labels, row norms).  GATED 2: the dense sweep with margins, for the
-// passes that the host knows must screen every row (no margins yet): no gate
-// pass, no indirection.
+// read (labels, row norms).  The entries come 64 at a time, four tiles' worth
+// in one coalesced 8-byte load per lane issued a whole group ahead of its
+// first use; a tile takes its 16 by a cross-lane read.  The load is
+// unconditional (index clamped, slots past the list's end marked after it
+// arrives), so every wait in the tile loop is a counted one, and in three
+// tiles of four the wait for a tile's rows leaves the next tile's row loads
+// in flight (in the first tile of a group the compiler waits for the tile's
+// rows before it issues the next tile's); with the lower totals in LDS no
+// global load's result is consumed inside the tile loop but the rows' and
+// the entries' (profiles/r10_s1_list_waits.txt).  The list instance keeps
+// two row buffers on every geometry (KM_S1_NBUF does not apply to it).
+// GATED 2: the dense sweep with margins, for the passes that the host knows
+// must screen every row (no margins yet): no gate pass, no indirection.
 template <int NS2, int NB, int MODE, bool REV = false, bool SSE = false, int GATED = 0>
 __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void k_s1(S1Args A) {
   if (*A.gate) return;  // a stopped batch (km_update_async): the rest of it is a no-op
@@ -423,6 +448,8 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
   float4* sRh = reinterpret_cast<float4*>(sRm + S1_WAVES * S1_RING);     // [S1_WAVES][S1_RING][4][2]
   // GATED: the ring rows' lower bound of the distance to every non-candidate
   float* sRl = reinterpret_cast<float*>(sRh + S1_WAVES * S1_RING * 8);   // [S1_WAVES][S1_RING]
+  // GATED: the clusters' lower totals (A.acc_dn, by label; pads 0), staged once
+  float* sAd = sRl + S1_WAVES * S1_RING;                                 // [KP]
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -438,6 +465,10 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
     }
     for (int i = threadIdx.x; i < KP; i += S1_WAVES * 64) sCn[i] = A.cn2o[i];
     for (int i = threadIdx.x; i < NT; i += S1_WAVES * 64) sPerm[i] = A.perm[i];
+    // (k_s1_shift ran before this pass on the same stream: these are the
+    // pass's totals, all zero after a non-finite shift or an epoch reset)
+    if constexpr (MARG)
+      for (int i = threadIdx.x; i < KP; i += S1_WAVES * 64) sAd[i] = i < A.k ? A.acc_dn[i] : 0.0f;
   }
   __syncthreads();
 
@@ -486,20 +517,42 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
   };
   struct BufList {
     float4 x[FQ / 4];
-    uint2 ent;  // the tile's entry of this lane: {row (>= n: none), the label it holds}
   };
   using Buf = typename std::conditional<LIST, BufList, BufDense>::type;
-  // LIST: this wave's work-list segment; the entry of the next tile to load
-  // is fetched one load ahead of its row, so the two dependent loads of a
-  // tile (entry, then row) never wait for each other in the loop
+  // LIST: this wave's work-list segment, walked in groups of 64 entries (four
+  // tiles): lane l of a group register holds entry 64 g + l, {row (>= n:
+  // none), the label it holds}, and tile 4 g + i takes lane 16 i + c16's.
+  // wg0: the group of the tile being processed, wg1: the next one (the load
+  // of a group's last tile reaches into it), wg2: the one after, in flight --
+  // fetched at the top of a group's trip, first used at the end of the next
+  // trip, and older than every row load outstanding when it is waited for
   const uint2* wlp = nullptr;
   uint32_t wln = 0;
-  uint2 wnext = make_uint2(0xFFFFFFFFu, 0u);
+  uint2 wg0 = make_uint2(0xFFFFFFFFu, 0u), wg1 = wg0, wg2 = wg0;
+  uint32_t wsub = 0;  // the tile being processed is tile wsub of its group
   const bool gscale = MARG && s1g_scale_ok(s);
+  // one unconditional 8-byte load per lane: the index clamped to the segment
+  // (allocated whole), no branch, so the waits behind it can count it
+  auto wfetch = [&](uint32_t g) { return wlp[min(g * 64u + (uint32_t)lane, A.seg - 1u)]; };
+  // slots past the list's end: no row (a select on the loaded value, so it
+  // runs where the value is first needed, not where the load is issued)
+  auto wmark = [&](uint32_t g, uint2 v) {
+    return make_uint2(g * 64u + (uint32_t)lane < wln ? v.x : 0xFFFFFFFFu, v.y);
+  };
+  // tile `sub` of a group: every quarter of the wave gets lanes 16 sub ..
+  // + 15 (through LDS hardware, no memory)
+  auto wpick = [&](uint32_t v, uint32_t sub) {
+    return (uint32_t)__builtin_amdgcn_ds_bpermute((int)((sub * 16u + (uint32_t)c16) * 4u), (int)v);
+  };
   if constexpr (LIST) {
-    wlp = A.wl + (size_t)gw * A.seg;
-    wln = min(A.wl_cnt[gw], A.seg);
-    if ((uint32_t)c16 < wln) wnext = wlp[c16];
+    // (wave-uniform by construction; said so, which keeps the segment's base,
+    // its length and the trip count in scalar registers and the walk's
+    // branches scalar)
+    const uint32_t gwu = (uint32_t)__builtin_amdgcn_readfirstlane((int)gw);
+    wlp = A.wl + (size_t)gwu * A.seg;
+    wln = (uint32_t)__builtin_amdgcn_readfirstlane((int)min(A.wl_cnt[gwu], A.seg));
+    wg0 = wmark(0u, wfetch(0u));
+    wg1 = wmark(1u, wfetch(1u));
   }
   // serpentine sweep (REV: its own instance, since a run-time select in the
   // row arithmetic cost the issue-bound c3 kernel 1.5%): step tiles mapped
@@ -508,12 +561,12 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
   auto load = [&](uint32_t tile, Buf& B) {
     uint32_t row;
     if constexpr (LIST) {
-      // (tiles are loaded in order 0, 1, 2, ...: wnext is tile's entry)
-      row = wnext.x;
-      B.ent = wnext;
-      const uint32_t e = (tile + 1u) * 16u + (uint32_t)c16;
-      wnext = make_uint2(0xFFFFFFFFu, 0u);
-      if (e < wln) wnext = wlp[e];
+      // (`tile`: 0 .. 3, the tile of the group being processed, or 4: the
+      // first tile of the next group.  Only the row is taken here; the tail
+      // picks the entry again, so no entry register rides with the buffer.
+      // Nothing but the row loads is issued: the group fetch has its own
+      // place at the top of the trip)
+      row = tile < 4u ? wpick(wg0.x, tile) : wpick(wg1.x, 0u);
     } else {
       row = tmap(tile) * 16u + (uint32_t)c16;
     }
@@ -699,7 +752,7 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
         // k_s1_gate: a listed row never keeps its old base)
         if (act && q == 0)
           A.marg[mt.x] = (kind == 0u && gscale)
-                             ? s1g_base(s1g_margin(fminf(lbo, sRl[wave * S1_RING + slot]), ubw), A.acc_dn[lab1])
+                             ? s1g_base(s1g_margin(fminf(lbo, sRl[wave * S1_RING + slot]), ubw), sAd[lab1])
                              : 0.0f;
       }
     } else {
@@ -711,10 +764,14 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
   // re-scoring ring
   auto tail = [&](uint32_t tile, const Buf& B, const float (&h)[2][4], float h2m) {
     uint32_t row;
-    if constexpr (LIST)
-      row = B.ent.x;
-    else
+    uint32_t lold = 0u;  // LIST: the label the entry carries
+    if constexpr (LIST) {
+      // the tile's entry, from the group register again (wsub: its place)
+      row = wpick(wg0.x, wsub);
+      lold = wpick(wg0.y, wsub);
+    } else {
       row = tmap(tile) * 16u + (uint32_t)c16;
+    }
     const bool valid = row < n;
     // full slot ids in the heads, (chain << MB) | member: distinct keys, so
     // float comparisons order them totally (f32 denormals are kept, and +0
@@ -813,7 +870,7 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
     const bool dec1 = ok && cnt == 1u && labm >= 0;
     int32_t old = 0;
     if constexpr (LIST)
-      old = (int32_t)min(B.ent.y, (uint32_t)(A.k - 1));
+      old = (int32_t)min(lold, (uint32_t)(A.k - 1));
     else if constexpr (MODE == 1)
       old = (int32_t)min((uint32_t)B.old, (uint32_t)(A.k - 1));
 #if KM_S1_ABL == 2
@@ -840,7 +897,7 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
       // `needy`, in rescore -- exactly one of the two
       if (valid && !needy && q == 0)
         A.marg[row] =
-            (dec1 && gscale) ? s1g_base(s1g_margin(s1g_lb(h2, RP, gr), s1g_ub(m, RP, gr)), A.acc_dn[labm]) : 0.0f;
+            (dec1 && gscale) ? s1g_base(s1g_margin(s1g_lb(h2, RP, gr), s1g_ub(m, RP, gr)), sAd[labm]) : 0.0f;
     }
     if constexpr (BATCH) {
       emit(valid && !needy, row, dec1 ? 0u : 2u, labm, 0, old);
@@ -1105,7 +1162,8 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
   // this wave's steps gw, gw + nw, ... of TT tiles each; NBUF register
   // buffers of rows: NBUF - 1 steps' loads in flight while one is processed
   // (loads past the end read row n - 1 and are never used)
-  constexpr int NBUF = KM_S1_NBUF > 0 ? KM_S1_NBUF : (NS2 == 1 && NB > 8 && S1_WAVES == 8 ? 3 : 2);
+  // (the list instance: always two, a group's four tiles alternate them)
+  constexpr int NBUF = LIST ? 2 : KM_S1_NBUF > 0 ? KM_S1_NBUF : (NS2 == 1 && NB > 8 && S1_WAVES == 8 ? 3 : 2);
   static_assert(!LIST || TT == 1, "the gated instance walks its list one tile per step");
   // steps st0, st0 + sw, ... below nst: the wave's share of the tiles, or
   // (GATED) the tiles of its own work list
@@ -1116,20 +1174,54 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
 #pragma unroll
     for (int u = 0; u < TT; ++u) load(st * TT + (uint32_t)u, BB[u]);
   };
+  if constexpr (LIST) {
+    // one trip per group of four tiles, unrolled, so that the group fetch is
+    // issued exactly once per trip and outside every branch: the waits then
+    // count it.  In issue order a trip's loads are: the fetch of group g + 2,
+    // then the rows of tiles 1, 2, 3 of this group and tile 0 of the next,
+    // each one tile ahead of its use.  A tile's wait for its rows leaves the
+    // next tile's four row loads (and, in the first tile, the fetch) in
+    // flight; the fetch is consumed at the end of the trip, when only the
+    // last row loads are younger (profiles/r10_s1_list_waits.txt lists the
+    // waits as compiled, tile 0 of a trip included, whose own rows the
+    // compiler waits for before it issues tile 1's)
+    static_assert(NBUF == 2 && TT == 1, "the list walk alternates two row buffers");
+    load(0u, b[0][0]);
+    for (uint32_t g = 0u; g * 4u < nst; ++g) {
+      wg2 = wfetch(g + 2u);
+      bool done = false;
 #pragma unroll
-  for (int u = 0; u + 1 < NBUF; ++u) load_step(st0 + (uint32_t)u * sw, b[u]);
-  // (st + 2 NBUF nw stays below 2^32: ntiles < 2^28, nw < 2^16)
-  for (uint32_t st = st0; st < nst; st += (uint32_t)NBUF * sw) {
-    bool done = false;
-#pragma unroll
-    for (int u = 0; u < NBUF; ++u) {
-      if (!done) {
-        load_step(st + (uint32_t)(u + NBUF - 1) * sw, b[(u + NBUF - 1) % NBUF]);
-        process(st + (uint32_t)u * sw, b[u]);
-        done = st + (uint32_t)(u + 1) * sw >= nst;
+      for (int i = 0; i < 4; ++i) {
+        if (!done) {
+          load((uint32_t)(i + 1), b[(i + 1) & 1][0]);
+          // (the next tile's row loads are issued here, ahead of this tile's
+          // wait for its own rows, not wherever the scheduler finds room)
+          __builtin_amdgcn_sched_barrier(0);
+          wsub = (uint32_t)i;
+          process(g * 4u + (uint32_t)i, b[i & 1]);
+          done = g * 4u + (uint32_t)(i + 1) >= nst;
+        }
       }
+      if (done) break;
+      wg0 = wg1;
+      wg1 = wmark(g + 2u, wg2);
     }
-    if (done) break;
+  } else {
+#pragma unroll
+    for (int u = 0; u + 1 < NBUF; ++u) load_step(st0 + (uint32_t)u * sw, b[u]);
+    // (st + 2 NBUF nw stays below 2^32: ntiles < 2^28, nw < 2^16)
+    for (uint32_t st = st0; st < nst; st += (uint32_t)NBUF * sw) {
+      bool done = false;
+#pragma unroll
+      for (int u = 0; u < NBUF; ++u) {
+        if (!done) {
+          load_step(st + (uint32_t)(u + NBUF - 1) * sw, b[(u + NBUF - 1) % NBUF]);
+          process(st + (uint32_t)u * sw, b[u]);
+          done = st + (uint32_t)(u + 1) * sw >= nst;
+        }
+      }
+      if (done) break;
+    }
   }
   if (rc) rescore(rc);
   if (lane == 0) {
