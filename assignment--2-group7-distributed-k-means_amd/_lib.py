@@ -69,6 +69,8 @@ SIGNATURES = {
     "km_load_begin": [_P, _I64, _I32],
     "km_load_rows": [_P, _I64, _PF, _I64],
     "km_generate_blobs": [_P, _I64, _I32, _I64, _I32, ctypes.c_float, ctypes.c_float, ctypes.c_uint64],
+    "km_set_weights": [_P, _I64, _PD, _I64],
+    "km_clear_weights": [_P],
     "km_sum_x": [_P, _PD],
     "km_set_sse": [_P, _I32],
     "km_set_screen": [_P, _I32],

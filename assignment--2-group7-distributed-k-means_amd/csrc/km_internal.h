@@ -190,6 +190,22 @@ hipError_t launch_stats_sorted(const float* X, const Geometry& g, const int32_t*
 // corrected per cluster to the float64 centroid at the flush)
 hipError_t launch_stats(const float* X, const Geometry& g, const int32_t* labels, double* stats, int n_cu,
                         const int* gate, hipStream_t s, const double* C64P = nullptr, const float* C32 = nullptr);
+// Weighted statistics (km_set_weights; fit(..., sample_weight=w)): labels in
+// place, one read of X.  stats = [k][d+1] weighted sums sum w x and ROW
+// counts, the SSE slot (sum w ||x - c||^2 with the float64 centroids C64 of
+// row stride c64s -- C64P and dp, or the small path's [k][d] -- and C32),
+// then wsum[k] = sum w per cluster at stats + k (d+1) + 1 (the update's
+// divisor).  launch_wstats: the k_stats scheme (LDS table, feature ranges,
+// wide rows); launch_wstats_sorted: the counting sort and weighted segment
+// sums where the table does not fit (wstats_needs_sort; scratch as
+// launch_stats_sorted)
+bool wstats_needs_sort(const Geometry& g);
+hipError_t launch_wstats(const float* X, const Geometry& g, const int32_t* labels, const double* w, double* stats,
+                         int n_cu, const int* gate, hipStream_t s, const double* C64 = nullptr, int c64s = 0,
+                         const float* C32 = nullptr);
+hipError_t launch_wstats_sorted(const float* X, const Geometry& g, const int32_t* labels, const double* w,
+                                double* stats, uint32_t* scratch, const double* C64P, int n_cu, const int* gate,
+                                hipStream_t s);
 // stats = [k][d+1] sums and counts, then the SSE slot stats[k (d+1)]
 // gate: the batch's stop flag (kernels of later iterations no-op once it is
 // set); stop_tol >= 0 lets k_finalize raise it (KM_STOP_*), < 0 never
@@ -199,11 +215,13 @@ hipError_t launch_stats(const float* X, const Geometry& g, const int32_t* labels
 // with compute_sse); the update adds the exact per-cluster correction
 // clear / C32, cmax (one-workgroup update only, update_one_ok): zero the
 // statistics after use and write the small path's images of the new centroids
+// wdiv != nullptr (weighted statistics): new = sum / wdiv[j] where the row
+// count is positive; nullptr: sum / count, today's arithmetic exactly
 bool update_one_ok(const Geometry& g);
 hipError_t launch_update(double* stats, const double* C64_old, const Geometry& g, double* C64_new,
                          double* work, int64_t* counts, const uint32_t* qcount, uint32_t nq, DevStatus* status,
                          int* gate, double stop_tol, int dev_repair, hipStream_t s, int clear = 0,
-                         float* C32 = nullptr, float* cmax = nullptr, int corr = 0);
+                         float* C32 = nullptr, float* cmax = nullptr, int corr = 0, const double* wdiv = nullptr);
 hipError_t launch_sum_x(const float* X, const Geometry& g, double* out, hipStream_t s);
 hipError_t launch_scatter_rows(const int64_t* ids, const double* rows, int32_t n, int d, double* C, hipStream_t s);
 hipError_t launch_gather_rows(const float* X, const Geometry& g, const int64_t* idx, int32_t n, double* out,

@@ -338,7 +338,8 @@ __device__ void update_one_body(double* __restrict__ stats, const double* __rest
                                 double* __restrict__ out, int64_t* __restrict__ counts, const double* __restrict__ sse,
                                 const uint32_t* __restrict__ qcount, uint32_t nq, DevStatus* __restrict__ st,
                                 int* __restrict__ gate, double stop_tol, int dev_repair, int clear,
-                                float* __restrict__ C32, float* __restrict__ cmax, int dp, int kp, int corr = 0);
+                                float* __restrict__ C32, float* __restrict__ cmax, int dp, int kp, int corr = 0,
+                                const double* __restrict__ wdiv = nullptr);
 
 // waves per SIMD at dp = 16 (KM_SMALL_WPE; c2 on one MI355X: 4 waves with the
 // row prefetch 146-147 us, 8 waves without it 154-161 us), the compiler's
@@ -4186,13 +4187,15 @@ __global__ __launch_bounds__(1024) void k_stats(const float* __restrict__ X, int
 
 // features per range: the widest (fewest blocks, longest row segments) among
 // those needing the fewest cluster ranges; segments stay >= 64 bytes
-static void stats_ranges(const Geometry& g, int* fr_out, int* kr_out) {
+// extra: table slots of a cluster beside its fr features (1: the count;
+// weighted statistics 2: the sum of weights and the count)
+static void stats_ranges(const Geometry& g, int* fr_out, int* kr_out, int extra = 1) {
   int best_fr = g.dp, best_kr = 0, best_ncr = 1 << 30;
   if (g.dp > 256) {
     // wide rows: any multiple of 4 dividing dp, at most 256 (dp = 2000: 80)
     for (int fr = 256; fr >= 16; fr -= 4) {
       if (g.dp % fr) continue;
-      int kr = (int)(STATS_LDS / ((size_t)(fr + 1) * 8));
+      int kr = (int)(STATS_LDS / ((size_t)(fr + extra) * 8));
       if (kr > g.k) kr = g.k;
       const int ncr = (g.k + kr - 1) / kr;
       if (ncr < best_ncr) {
@@ -4206,7 +4209,7 @@ static void stats_ranges(const Geometry& g, int* fr_out, int* kr_out) {
     return;
   }
   for (int fr = g.dp; fr >= 16 && g.dp % fr == 0 && fr % 4 == 0; fr /= 2) {
-    int kr = (int)(STATS_LDS / ((size_t)(fr + 1) * 8));
+    int kr = (int)(STATS_LDS / ((size_t)(fr + extra) * 8));
     if (kr > g.k) kr = g.k;
     const int ncr = (g.k + kr - 1) / kr;
     if (ncr < best_ncr) {
@@ -4247,6 +4250,175 @@ hipError_t launch_stats(const float* X, const Geometry& g, const int32_t* labels
   else
     hipLaunchKernelGGL((k_stats<false>), dim3((unsigned)bx, (unsigned)ranges, (unsigned)franges), dim3(1024),
                        lds, s, X, g.n, g.d, g.dp, g.k, labels, stats, kr, fr, rpb, C64P, C32, (double*)nullptr, gate);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Weighted partial statistics (fit(..., sample_weight=w)): the k_stats scheme
+// with a float64 weight per row.  Per cluster S = sum w x into the sum slots,
+// the row count n into the count slot (clusters are empty by rows, not by
+// weight) and W = sum w into wsum[k] (the k doubles behind the SSE slot: the
+// update's divisor).  The weights of a chunk of 64 rows come from one
+// coalesced 8-byte load per lane and reach the rows' lane groups by shuffle,
+// like the labels.  An LDS table row is fr + 2 slots: features, W, n; W and n
+// reach the global statistics from feature range 0 only.
+// SSE: sum w (x - c)^2, by the same fp32-image identity with weighted sums:
+//   sum w (x - c)^2 = sum w (x - c')^2 - 2 delta (S - W c') + W delta^2
+// (every feature range keeps W in its table for the correction).
+// ---------------------------------------------------------------------------
+template <bool SSE = false>
+__global__ __launch_bounds__(1024) void k_wstats(const float* __restrict__ X, int64_t n, int d, int dp, int k,
+                                                 const int32_t* __restrict__ labels, const double* __restrict__ w,
+                                                 double* __restrict__ stats, double* __restrict__ wsum, int kr,
+                                                 int fr, int64_t rows_per_block, const double* __restrict__ C64,
+                                                 int c64s, const float* __restrict__ C32, double* __restrict__ sse,
+                                                 const int* __restrict__ gate) {
+  if (*gate) return;  // a stopped batch (km_update_async): the rest of it is a no-op
+  if constexpr (!SSE) sse = nullptr;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  double* tab = reinterpret_cast<double*>(smem);
+  // feature f0 + 4m + c at slot c*L + m (as k_stats), W at slot fr, n at fr + 1
+  const int RS = fr + 2;
+  const int L = fr / 4;
+  const int c0 = blockIdx.y * kr;
+  const int c1 = min(k, c0 + kr);
+  const int f0 = blockIdx.z * fr;
+  const bool counts = blockIdx.z == 0;
+  const int nent = (c1 - c0) * RS;
+  for (int i = threadIdx.x; i < nent; i += blockDim.x) tab[i] = 0.0;
+  __syncthreads();
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
+  const int64_t r1 = min(n, r0 + rows_per_block);
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int nwaves = blockDim.x >> 6;
+  const int P = 64 / L;
+  const int q = lane / L;
+  const int mm = lane % L;
+  const bool act = q < P;
+  constexpr int U = SSE ? 6 : 8;
+  double ss = 0.0;
+  for (int64_t cr = r0 + (int64_t)wave * 64; cr < r1; cr += (int64_t)nwaves * 64) {
+    const int nrow = (int)min((int64_t)64, r1 - cr);
+    const int labreg = lane < nrow ? labels[cr + lane] : -1;
+    const double wreg = lane < nrow ? w[cr + lane] : 0.0;
+    if (lane < nrow && labreg >= c0 && labreg < c1) {
+      double* t = tab + (labreg - c0) * RS + fr;
+      if (counts || sse) atomicAdd(t, wreg);
+      if (counts) atomicAdd(t + 1, 1.0);
+    }
+    const float* base = X + cr * dp + f0;
+    for (int rb = 0; rb < nrow; rb += P * U) {
+      float4 v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int rr = rb + u * P + q;
+        v[u] = (act && rr < nrow) ? *reinterpret_cast<const float4*>(base + (size_t)rr * dp + 4 * mm)
+                                  : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+      int labs[U];
+      double wv[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        labs[u] = __shfl(labreg, (rb + u * P + q) & 63);
+        wv[u] = __shfl(wreg, (rb + u * P + q) & 63);
+      }
+      float4 cg[U];
+      if (sse) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int rr = rb + u * P + q;
+          const bool mine = act && rr < nrow && labs[u] >= c0 && labs[u] < c1;
+          cg[u] = mine ? *reinterpret_cast<const float4*>(C32 + (size_t)labs[u] * dp + f0 + 4 * mm)
+                       : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int rr = rb + u * P + q;
+        const int lab = labs[u];
+        if (act && rr < nrow && lab >= c0 && lab < c1) {
+          const double wr = wv[u];
+          double* t = tab + (lab - c0) * RS + mm;
+          atomicAdd(t, wr * (double)v[u].x);
+          atomicAdd(t + L, wr * (double)v[u].y);
+          atomicAdd(t + 2 * L, wr * (double)v[u].z);
+          atomicAdd(t + 3 * L, wr * (double)v[u].w);
+          if (sse) {  // padded features are 0 - 0
+            const float4 c = cg[u];
+            const double t0 = (double)v[u].x - (double)c.x, t1 = (double)v[u].y - (double)c.y;
+            const double t2 = (double)v[u].z - (double)c.z, t3 = (double)v[u].w - (double)c.w;
+            ss = fma(wr * t0, t0, ss);
+            ss = fma(wr * t1, t1, ss);
+            ss = fma(wr * t2, t2, ss);
+            ss = fma(wr * t3, t3, ss);
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const int d1 = d + 1;
+  for (int i = threadIdx.x; i < nent; i += blockDim.x) {
+    const int j = i / RS;
+    const int p = i - j * RS;
+    const double v = tab[i];
+    if (p >= fr) {
+      if (!counts || v == 0.0) continue;  // W and n only from feature range 0
+      if (p == fr)
+        atomicAdd(wsum + c0 + j, v);
+      else
+        atomicAdd(stats + (size_t)(c0 + j) * d1 + d, v);
+      continue;
+    }
+    const int f = f0 + 4 * (p % L) + p / L;
+    if (f >= d) continue;  // zero padding
+    if (sse) {
+      // delta (S - W c') and W delta^2 of this (cluster, feature)
+      const double W = tab[j * RS + fr];
+      if (W != 0.0) {
+        const double cp = (double)C32[(size_t)(c0 + j) * dp + f];
+        const double dl = C64[(size_t)(c0 + j) * c64s + f] - cp;
+        ss += dl * (W * dl - 2.0 * (v - W * cp));
+      }
+    }
+    if (v == 0.0) continue;
+    atomicAdd(stats + (size_t)(c0 + j) * d1 + f, v);
+  }
+  if (sse) {
+    ss = wave_sum(ss);
+    if (lane == 0 && ss != 0.0) atomicAdd(sse, ss);
+  }
+}
+
+hipError_t launch_wstats(const float* X, const Geometry& g, const int32_t* labels, const double* w, double* stats,
+                         int n_cu, const int* gate, hipStream_t s, const double* C64, int c64s, const float* C32) {
+  if (g.n == 0) return hipSuccess;
+  if (!w || (C64 && !C32)) return hipErrorInvalidValue;
+  if (g.dp > WIDE_MAX_DP || g.dp % 4) return hipErrorInvalidValue;
+  int fr = 0, kr = 0;
+  stats_ranges(g, &fr, &kr, 2);
+  if (kr < 1) return hipErrorInvalidValue;
+  const int ranges = (g.k + kr - 1) / kr;
+  const int franges = g.dp / fr;
+  const size_t lds = (size_t)kr * (fr + 2) * 8;
+  int per_cu = (int)((160 * 1024) / (lds + 1024));
+  if (per_cu < 1) per_cu = 1;
+  if (per_cu > 2) per_cu = 2;
+  int64_t bx = (int64_t)n_cu * per_cu / (ranges * franges);
+  if (bx < 1) bx = 1;
+  const int64_t min_rows = 4096;
+  if (bx > (g.n + min_rows - 1) / min_rows) bx = (g.n + min_rows - 1) / min_rows;
+  int64_t rpb = (g.n + bx - 1) / bx;
+  rpb = (rpb + 63) / 64 * 64;
+  double* sse = stats + (size_t)g.k * (g.d + 1);
+  double* wsum = sse + 1;
+  if (C64)
+    hipLaunchKernelGGL((k_wstats<true>), dim3((unsigned)bx, (unsigned)ranges, (unsigned)franges), dim3(1024), lds, s, X,
+                       g.n, g.d, g.dp, g.k, labels, w, stats, wsum, kr, fr, rpb, C64, c64s, C32, sse, gate);
+  else
+    hipLaunchKernelGGL((k_wstats<false>), dim3((unsigned)bx, (unsigned)ranges, (unsigned)franges), dim3(1024), lds, s, X,
+                       g.n, g.d, g.dp, g.k, labels, w, stats, wsum, kr, fr, rpb, C64, c64s, C32, (double*)nullptr, gate);
   return hipGetLastError();
 }
 
@@ -4503,6 +4675,101 @@ __global__ void k_put_counts(const uint32_t* __restrict__ cnt, int k, int d, dou
   if (j < k) stats[(size_t)j * (d + 1) + d] = (double)cnt[j];
 }
 
+// Weighted segmented sums (fit(..., sample_weight=w)): k_segsum with the
+// row's float64 weight gathered beside the row (w[perm[pos]], 8 bytes per
+// row through the same index).  The lane group accumulates S += w x; its
+// first lane also W += w, flushed to wsum[cluster] with the sums.  The SSE
+// residuals w (x - c)^2 to the float64 centroid ride along as in k_segsum.
+template <int L>  // lanes per row = dp / 4
+__global__ __launch_bounds__(256) void k_wsegsum(const float* __restrict__ X, int d, int64_t n,
+                                                 const uint32_t* __restrict__ perm, const int32_t* __restrict__ slab,
+                                                 const double* __restrict__ w, double* __restrict__ stats,
+                                                 double* __restrict__ wsum, const double* __restrict__ C64P,
+                                                 double* __restrict__ sse, const int* __restrict__ gate) {
+  if (*gate) return;  // a stopped batch (km_update_async): the rest of it is a no-op
+  constexpr int P = 64 / L;
+  constexpr int U = 4;
+  constexpr int DP = 4 * L;
+  const int lane = threadIdx.x & 63;
+  const int q = lane / L;
+  const int m = lane % L;
+  const bool act = q < P;
+  const int64_t gw = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
+  const int64_t per = (n + nw - 1) / nw;
+  const int64_t p0 = gw * per;
+  const int64_t p1 = p0 + per < n ? p0 + per : n;
+  const int d1 = d + 1;
+  int cur = -1;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, aw = 0.0;
+  double c0 = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0, ss = 0.0;
+  auto flush = [&]() {
+    if (cur >= 0) {
+      double* o = stats + (size_t)cur * d1 + 4 * m;
+      if (4 * m + 0 < d) atomicAdd(o + 0, a0);
+      if (4 * m + 1 < d) atomicAdd(o + 1, a1);
+      if (4 * m + 2 < d) atomicAdd(o + 2, a2);
+      if (4 * m + 3 < d) atomicAdd(o + 3, a3);
+      if (m == 0) atomicAdd(wsum + cur, aw);
+    }
+    a0 = a1 = a2 = a3 = aw = 0.0;
+  };
+  for (int64_t base = p0; act && base < p1; base += P * U) {
+    float4 v[U];
+    int lb[U];
+    double wv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t pos = base + u * P + q;
+      if (pos < p1) {
+        const uint32_t row = perm[pos];
+        lb[u] = slab[pos];
+        wv[u] = w[row];
+        v[u] = *reinterpret_cast<const float4*>(X + (size_t)row * DP + 4 * m);
+      } else {
+        lb[u] = -1;
+        wv[u] = 0.0;
+        v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (lb[u] < 0) continue;
+      if (lb[u] != cur) {
+        flush();
+        cur = lb[u];
+        if (C64P) {
+          const double2 ca = *reinterpret_cast<const double2*>(C64P + (size_t)cur * DP + 4 * m);
+          const double2 cb = *reinterpret_cast<const double2*>(C64P + (size_t)cur * DP + 4 * m + 2);
+          c0 = ca.x;
+          c1 = ca.y;
+          c2 = cb.x;
+          c3 = cb.y;
+        }
+      }
+      const double wr = wv[u];
+      a0 = fma(wr, (double)v[u].x, a0);
+      a1 = fma(wr, (double)v[u].y, a1);
+      a2 = fma(wr, (double)v[u].z, a2);
+      a3 = fma(wr, (double)v[u].w, a3);
+      aw += wr;
+      if (C64P) {  // padded features are 0 - 0
+        const double t0 = (double)v[u].x - c0, t1 = (double)v[u].y - c1;
+        const double t2 = (double)v[u].z - c2, t3 = (double)v[u].w - c3;
+        ss = fma(wr * t0, t0, ss);
+        ss = fma(wr * t1, t1, ss);
+        ss = fma(wr * t2, t2, ss);
+        ss = fma(wr * t3, t3, ss);
+      }
+    }
+  }
+  if (act) flush();
+  if (C64P) {
+    ss = wave_sum(ss);
+    if (lane == 0 && ss != 0.0) atomicAdd(sse, ss);
+  }
+}
+
 size_t sorted_stats_words(int64_t n, int k) { return 2 * (size_t)n + 3 * (size_t)k + 64; }
 
 // the range-tiled k_stats reads X once per LDS-sized cluster range; from three
@@ -4517,8 +4784,10 @@ bool stats_needs_sort(const Geometry& g) {
   return kr == 0 || (g.k + kr - 1) / kr >= min_ranges;
 }
 
-hipError_t launch_stats_sorted(const float* X, const Geometry& g, const int32_t* labels, double* stats,
-                               uint32_t* scratch, const double* C64P, int n_cu, const int* gate, hipStream_t s) {
+// w != nullptr: the weighted segment sums (k_wsegsum) behind the same sort
+static hipError_t stats_sorted(const float* X, const Geometry& g, const int32_t* labels, const double* w,
+                               double* stats, uint32_t* scratch, const double* C64P, int n_cu, const int* gate,
+                               hipStream_t s) {
   if (g.n == 0) return hipSuccess;
   if (g.dp > 256) return hipErrorInvalidValue;
   uint32_t* cnt = scratch;
@@ -4544,18 +4813,49 @@ hipError_t launch_stats_sorted(const float* X, const Geometry& g, const int32_t*
   const int64_t nsorted = g.n;
   int64_t wb = (int64_t)n_cu * 8;
   const unsigned grid = (unsigned)wb;
+  double* sse = stats + (size_t)g.k * (g.d + 1);
+#define KM_SEGSUM(L)                                                                                              \
+  do {                                                                                                            \
+    if (w)                                                                                                        \
+      hipLaunchKernelGGL(k_wsegsum<L>, dim3(grid), dim3(256), 0, s, X, g.d, nsorted, perm, slab, w, stats, sse + 1, \
+                         C64P, sse, gate);                                                                        \
+    else                                                                                                          \
+      hipLaunchKernelGGL(k_segsum<L>, dim3(grid), dim3(256), 0, s, X, g.d, nsorted, perm, slab, stats, C64P, sse,  \
+                         gate);                                                                                   \
+  } while (0)
   switch (g.dp / 4) {
-    case 4: hipLaunchKernelGGL(k_segsum<4>, dim3(grid), dim3(256), 0, s, X, g.d, nsorted, perm, slab, stats, C64P, stats + (size_t)g.k * (g.d + 1), gate); break;
-    case 8: hipLaunchKernelGGL(k_segsum<8>, dim3(grid), dim3(256), 0, s, X, g.d, nsorted, perm, slab, stats, C64P, stats + (size_t)g.k * (g.d + 1), gate); break;
-    case 12: hipLaunchKernelGGL(k_segsum<12>, dim3(grid), dim3(256), 0, s, X, g.d, nsorted, perm, slab, stats, C64P, stats + (size_t)g.k * (g.d + 1), gate); break;
-    case 16: hipLaunchKernelGGL(k_segsum<16>, dim3(grid), dim3(256), 0, s, X, g.d, nsorted, perm, slab, stats, C64P, stats + (size_t)g.k * (g.d + 1), gate); break;
-    case 24: hipLaunchKernelGGL(k_segsum<24>, dim3(grid), dim3(256), 0, s, X, g.d, nsorted, perm, slab, stats, C64P, stats + (size_t)g.k * (g.d + 1), gate); break;
-    case 32: hipLaunchKernelGGL(k_segsum<32>, dim3(grid), dim3(256), 0, s, X, g.d, nsorted, perm, slab, stats, C64P, stats + (size_t)g.k * (g.d + 1), gate); break;
-    case 48: hipLaunchKernelGGL(k_segsum<48>, dim3(grid), dim3(256), 0, s, X, g.d, nsorted, perm, slab, stats, C64P, stats + (size_t)g.k * (g.d + 1), gate); break;
-    case 64: hipLaunchKernelGGL(k_segsum<64>, dim3(grid), dim3(256), 0, s, X, g.d, nsorted, perm, slab, stats, C64P, stats + (size_t)g.k * (g.d + 1), gate); break;
+    case 4: KM_SEGSUM(4); break;
+    case 8: KM_SEGSUM(8); break;
+    case 12: KM_SEGSUM(12); break;
+    case 16: KM_SEGSUM(16); break;
+    case 24: KM_SEGSUM(24); break;
+    case 32: KM_SEGSUM(32); break;
+    case 48: KM_SEGSUM(48); break;
+    case 64: KM_SEGSUM(64); break;
     default: return hipErrorInvalidValue;
   }
+#undef KM_SEGSUM
   return hipGetLastError();
+}
+
+hipError_t launch_stats_sorted(const float* X, const Geometry& g, const int32_t* labels, double* stats,
+                               uint32_t* scratch, const double* C64P, int n_cu, const int* gate, hipStream_t s) {
+  return stats_sorted(X, g, labels, nullptr, stats, scratch, C64P, n_cu, gate, s);
+}
+
+// the weighted statistics' table row has one slot more (stats_ranges extra = 2)
+bool wstats_needs_sort(const Geometry& g) {
+  if (g.dp > 256) return false;
+  int fr = 0, kr = 0;
+  stats_ranges(g, &fr, &kr, 2);
+  return kr == 0 || (g.k + kr - 1) / kr >= 3;
+}
+
+hipError_t launch_wstats_sorted(const float* X, const Geometry& g, const int32_t* labels, const double* w,
+                                double* stats, uint32_t* scratch, const double* C64P, int n_cu, const int* gate,
+                                hipStream_t s) {
+  if (!w) return hipErrorInvalidValue;
+  return stats_sorted(X, g, labels, w, stats, scratch, C64P, n_cu, gate, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -4578,17 +4878,19 @@ __device__ __forceinline__ double sse_corr_term(double o, double S, double cnt) 
 
 __global__ __launch_bounds__(64) void k_update(const double* __restrict__ stats, const double* __restrict__ old,
                                                int k, int d, double* __restrict__ out, double* __restrict__ work,
-                                               int64_t* __restrict__ counts, const int* __restrict__ gate, int corr) {
+                                               int64_t* __restrict__ counts, const int* __restrict__ gate, int corr,
+                                               const double* __restrict__ wdiv) {
   if (*gate) return;  // a stopped batch (km_update_async): the rest of it is a no-op
   const int j = blockIdx.x;
   const int lane = threadIdx.x;
   const int d1 = d + 1;
   const double cnt = stats[(size_t)j * d1 + d];
+  const double div = wdiv ? wdiv[j] : cnt;  // weighted statistics: the cluster's sum of weights
   double sh = 0.0, nf = 0.0, cr = 0.0;
   for (int f = lane; f < d; f += 64) {
     const double S = stats[(size_t)j * d1 + f];
     const double o = old[(size_t)j * d + f];
-    const double nv = (cnt > 0.0) ? S / cnt : o;
+    const double nv = (cnt > 0.0) ? S / div : o;
     out[(size_t)j * d + f] = nv;
     const double df = nv - o;
     sh = fma(df, df, sh);
@@ -4698,7 +5000,8 @@ __device__ void update_one_body(double* __restrict__ stats, const double* __rest
                                 double* __restrict__ out, int64_t* __restrict__ counts, const double* __restrict__ sse,
                                 const uint32_t* __restrict__ qcount, uint32_t nq, DevStatus* __restrict__ st,
                                 int* __restrict__ gate, double stop_tol, int dev_repair, int clear,
-                                float* __restrict__ C32, float* __restrict__ cmax, int dp, int kp, int corr) {
+                                float* __restrict__ C32, float* __restrict__ cmax, int dp, int kp, int corr,
+                                const double* __restrict__ wdiv) {
   auto ld = [](const double* p) {
     if constexpr (COHERENT)
       return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -4715,12 +5018,13 @@ __device__ void update_one_body(double* __restrict__ stats, const double* __rest
   unsigned int cmb = 0u;  // max ||c|| bits (k_prep_small)
   for (int j = wave; j < k; j += nw) {
     const double cnt = ld(stats + (size_t)j * d1 + d);
+    const double div = wdiv ? wdiv[j] : cnt;  // weighted statistics: the cluster's sum of weights
     double sh = 0.0, nfl = 0.0, nn = 0.0, cr = 0.0;
     for (int f = lane; f < (C32 ? dp : d); f += 64) {
       if (f < d) {
         const double S = ld(stats + (size_t)j * d1 + f);
         const double o = old[(size_t)j * d + f];
-        const double nv = (cnt > 0.0) ? S / cnt : o;
+        const double nv = (cnt > 0.0) ? S / div : o;
         out[(size_t)j * d + f] = nv;
         const double df = nv - o;
         sh = fma(df, df, sh);
@@ -4812,7 +5116,8 @@ __global__ __launch_bounds__(1024) void k_update_one(double* __restrict__ stats,
                                                      const uint32_t* __restrict__ qcount, uint32_t nq,
                                                      DevStatus* __restrict__ st, int* __restrict__ gate,
                                                      double stop_tol, int dev_repair, int clear, float* __restrict__ C32,
-                                                     float* __restrict__ cmax, int dp, int kp, int corr) {
+                                                     float* __restrict__ cmax, int dp, int kp, int corr,
+                                                     const double* __restrict__ wdiv) {
   if (*gate) {
     if (threadIdx.x == 0) {
       st->ran = 0;
@@ -4821,7 +5126,7 @@ __global__ __launch_bounds__(1024) void k_update_one(double* __restrict__ stats,
     return;
   }
   update_one_body<false>(stats, old, k, d, out, counts, sse, qcount, nq, st, gate, stop_tol, dev_repair, clear, C32,
-                         cmax, dp, kp, corr);
+                         cmax, dp, kp, corr, wdiv);
 }
 
 bool update_one_ok(const Geometry& g) { return g.k <= 64 && (size_t)g.k * g.d <= 16384; }
@@ -4829,16 +5134,16 @@ bool update_one_ok(const Geometry& g) { return g.k <= 64 && (size_t)g.k * g.d <=
 hipError_t launch_update(double* stats, const double* C64_old, const Geometry& g, double* C64_new,
                          double* work, int64_t* counts, const uint32_t* qcount, uint32_t nq, DevStatus* status,
                          int* gate, double stop_tol, int dev_repair, hipStream_t s, int clear, float* C32,
-                         float* cmax, int corr) {
+                         float* cmax, int corr, const double* wdiv) {
   if (update_one_ok(g)) {  // at most 4 clusters per wave (c3: 2 launches, 11 vs 37 us)
     hipLaunchKernelGGL(k_update_one, dim3(1), dim3(1024), 0, s, stats, C64_old, g.k, g.d, C64_new, counts,
                        stats + (size_t)g.k * (g.d + 1), qcount, nq, status, gate, stop_tol, dev_repair, clear, C32,
-                       cmax, g.dp, g.kp, corr);
+                       cmax, g.dp, g.kp, corr, wdiv);
     return hipGetLastError();
   }
   if (clear || C32) return hipErrorInvalidValue;  // only the one-workgroup update clears / prepares
   hipLaunchKernelGGL(k_update, dim3(g.k), dim3(64), 0, s, stats, C64_old, g.k, g.d, C64_new, work, counts, gate,
-                     corr);
+                     corr, wdiv);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_finalize, dim3(1), dim3(256), 0, s, work, counts, g.k, stats + (size_t)g.k * (g.d + 1),

@@ -55,6 +55,9 @@ bool fused_disabled() { return km::diag_env("KM_FUSED", 1) == 0; }
 
 // [k][d+1] sums and counts, then the SSE slot
 size_t stats_len(const km::Geometry& g) { return (size_t)g.k * (g.d + 1) + 1; }
+// with weights (km_set_weights) k more doubles follow: the clusters' sums of
+// weights.  The context's own buffers are always allocated with them
+size_t stats_cap(const km::Geometry& g) { return stats_len(g) + (size_t)g.k; }
 
 int choose_dp(int d) {
   for (int v : kAllowedDp)
@@ -141,6 +144,10 @@ struct km_ctx {
   bool rep_armed = false;
   // data
   float* X = nullptr;
+  // km_set_weights: one float64 weight per local row; non-null = weighted
+  // mode (labels by run_assign(c, false), then the weighted statistics pass;
+  // no delta statistics, row gate, folded small update or k_s1 SSE correction)
+  double* w = nullptr;
   int32_t* labels = nullptr;
   km::QEntry* queue = nullptr;
   uint32_t* qcount = nullptr;
@@ -261,6 +268,9 @@ struct km_ctx {
 
 namespace {
 
+// doubles of the stats buffer a caller sees, all-reduces and binds
+size_t stats_len(const km_ctx* c) { return c->w ? stats_cap(c->g) : stats_len(c->g); }
+
 struct ProfScope {
   km_ctx* c;
   int kind;
@@ -363,6 +373,7 @@ void free_seed(km_ctx* c) {
 void free_data(km_ctx* c) {
   free_seed(c);  // the state describes the rows being released
   dfree(c->X);
+  dfree(c->w);
   dfree(c->labels);
   dfree(c->queue);
   dfree(c->qcount);
@@ -512,7 +523,7 @@ km::SmallTail small_tail(km_ctx* c) {
 // update), no device repair behind it
 bool fold_ok(km_ctx* c) {
   return c->in_batch && c->path == 1 && km::update_one_ok(c->g) && c->stats == c->stats_own && !c->stats_exported &&
-         !(c->rep_enabled && c->rep_armed);
+         !(c->rep_enabled && c->rep_armed) && !c->w;
 }
 
 int run_assign(km_ctx* c, bool with_stats);
@@ -558,7 +569,7 @@ int apply_stats(km_ctx* c, const double** upd_src = nullptr, bool clear = false)
   const bool keep = kind == 2 || kind == 1;
   const bool zero = kind == 2 && clear && upd_src;
   if (keep)
-    KM_HIP(km::launch_s1_apply(c->stats, c->stats_full, (int64_t)stats_len(c->g), kind == 2 ? (zero ? 2 : 1) : 0,
+    KM_HIP(km::launch_s1_apply(c->stats, c->stats_full, (int64_t)stats_len(c), kind == 2 ? (zero ? 2 : 1) : 0,
                                c->gate, c->stream));
   if (zero) {
     *upd_src = c->stats_full;
@@ -606,7 +617,7 @@ int run_assign(km_ctx* c, bool with_stats) {
   c->bounds_valid = false;
   if (!use_s1(c, with_stats)) c->gate_init_dev = nullptr;
   if (with_stats) c->last_gated = false;
-  if (with_stats && !c->stats_clean) KM_HIP(hipMemsetAsync(c->stats, 0, sizeof(double) * stats_len(g), c->stream));
+  if (with_stats && !c->stats_clean) KM_HIP(hipMemsetAsync(c->stats, 0, sizeof(double) * stats_len(c), c->stream));
   if (with_stats) c->stats_clean = false;
   if (c->path == 1) {
     ProfScope ps(c, KM_K_ASSIGN, true);
@@ -786,6 +797,47 @@ int run_assign(km_ctx* c, bool with_stats) {
   }
   return KM_OK;
 }
+
+// km_assign_stats with weights: exact labels on whichever path the geometry
+// takes, then the weighted statistics pass (X is read twice per iteration).
+// Always full sums: nothing of the delta machinery survives the pass
+int run_assign_weighted(km_ctx* c) {
+  const km::Geometry& g = c->g;
+  int rc = run_assign(c, false);
+  if (rc != KM_OK) return rc;
+  c->delta_ready = false;  // the labels are this pass's, stats_full describes none
+  c->stats_pending = 0;
+  c->last_delta = false;
+  c->last_gated = false;
+  c->sse_corr = false;
+  c->gate_init_dev = nullptr;
+  KM_HIP(hipMemsetAsync(c->stats, 0, sizeof(double) * stats_len(c), c->stream));
+  c->stats_clean = false;
+  const bool sse = c->want_sse;
+  ProfScope ps(c, KM_K_STATS);
+  if (km::wstats_needs_sort(g)) {
+    const size_t words = km::sorted_stats_words(g.n, g.k);
+    if (words > c->sort_words) {
+      dfree(c->sort_scratch);
+      KM_HIP(hipMalloc(&c->sort_scratch, sizeof(uint32_t) * words));
+      c->sort_words = words;
+    }
+    // (path 1 keeps no padded float64 image: its geometries never sort)
+    KM_REQUIRE(c->path == 2, KM_ERR_UNSUPPORTED, "km_assign_stats: weighted statistics need the MFMA path at this k");
+    KM_HIP(km::launch_wstats_sorted(c->X, g, c->labels, c->w, c->stats, c->sort_scratch, sse ? c->C64P : nullptr,
+                                    c->n_cu, c->gate, c->stream));
+  } else {
+    // the small path keeps no padded float64 image: its centroids are [k][d]
+    const double* c64 = c->path == 1 ? c->C64_cur : c->C64P;
+    KM_HIP(km::launch_wstats(c->X, g, c->labels, c->w, c->stats, c->n_cu, c->gate, c->stream, sse ? c64 : nullptr,
+                             c->path == 1 ? g.d : g.dp, sse ? c->C32 : nullptr));
+  }
+  return KM_OK;
+}
+
+// the update's divisor: the clusters' sums of weights behind the SSE slot of
+// the buffer it reads, or null (row counts)
+const double* wdiv_of(const km_ctx* c, const double* src) { return c->w ? src + stats_len(c->g) : nullptr; }
 
 }  // namespace
 
@@ -994,6 +1046,62 @@ int km_load_rows(km_ctx* c, int64_t row0, const float* rows, int64_t nrows) {
   return KM_OK;
 }
 
+// a change of mode (weights set <-> none) changes the length of the stats
+// buffer and what the statistics in flight mean
+static int weights_mode_changed(km_ctx* c) {
+  c->delta_ready = false;
+  c->bounds_valid = false;
+  c->last_gated = false;
+  c->last_delta = false;
+  c->stats_pending = 0;
+  c->sse_corr = false;
+  c->stats_clean = false;
+  c->stats = c->stats_own;  // an external buffer has the old length: bind again
+  return KM_OK;
+}
+
+int km_set_weights(km_ctx* c, int64_t row0, const double* w, int64_t nrows) {
+  KM_REQUIRE(c && c->loaded, KM_ERR_STATE, "km_set_weights: call km_load_begin first");
+  KM_REQUIRE(!c->in_batch, KM_ERR_STATE, "km_set_weights: inside a batch");
+  KM_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= c->g.n, KM_ERR_ARG, "km_set_weights: rows out of range");
+  KM_REQUIRE(nrows == 0 || w, KM_ERR_ARG, "km_set_weights: null weights");
+  KM_HIP(hipSetDevice(c->device));
+  {
+    const int rcf = flush_assign(c);  // decided without weights: it runs that way
+    if (rcf != KM_OK) return rcf;
+  }
+  KM_HIP(hipStreamSynchronize(c->stream));
+  if (!c->w) {
+    // rows the caller never sets weigh 1
+    const int64_t rows = std::max<int64_t>(c->g.n, 1);
+    std::vector<double> ones((size_t)std::min<int64_t>(rows, (int64_t)1 << 20), 1.0);
+    KM_HIP(hipMalloc(&c->w, sizeof(double) * rows));
+    for (int64_t r = 0; r < rows; r += (int64_t)ones.size())
+      KM_HIP(hipMemcpy(c->w + r, ones.data(), sizeof(double) * std::min<int64_t>((int64_t)ones.size(), rows - r),
+                       hipMemcpyHostToDevice));
+    weights_mode_changed(c);
+  }
+  // chunked like km_load_rows (pageable source: each chunk is staged by the runtime)
+  const int64_t per = (int64_t)8 << 20;  // 64 MiB
+  for (int64_t r = 0; r < nrows; r += per) {
+    const int64_t m = std::min(per, nrows - r);
+    KM_HIP(hipMemcpyAsync(c->w + row0 + r, w + r, sizeof(double) * m, hipMemcpyHostToDevice, c->stream));
+    KM_HIP(hipStreamSynchronize(c->stream));
+  }
+  c->delta_ready = false;
+  return KM_OK;
+}
+
+int km_clear_weights(km_ctx* c) {
+  KM_REQUIRE(c, KM_ERR_ARG, "null ctx");
+  KM_REQUIRE(!c->in_batch, KM_ERR_STATE, "km_clear_weights: inside a batch");
+  if (!c->w) return KM_OK;
+  KM_HIP(hipSetDevice(c->device));
+  KM_HIP(hipStreamSynchronize(c->stream));
+  dfree(c->w);
+  return weights_mode_changed(c);
+}
+
 int km_generate_blobs(km_ctx* c, int64_t n, int32_t d, int64_t global_row0, int32_t n_centers, float box,
                       float stddev, uint64_t seed) {
   KM_REQUIRE(c, KM_ERR_ARG, "null ctx");
@@ -1084,7 +1192,7 @@ int km_set_centroids(km_ctx* c, const double* C, int32_t k, int32_t d) {
     c->bal = c->bnd + 4;  // [0, 1]: screening-bound constants; bal[0..10]: fast screen image maxima and bound constants
     KM_HIP(hipMalloc(&c->cmax, sizeof(float)));
     KM_HIP(hipMalloc(&c->cabs, sizeof(float)));
-    KM_HIP(hipMalloc(&c->stats_own, sizeof(double) * stats_len(c->g)));
+    KM_HIP(hipMalloc(&c->stats_own, sizeof(double) * stats_cap(c->g)));
     KM_HIP(hipMalloc(&c->work, sizeof(double) * 3 * k));
     KM_HIP(hipMalloc(&c->counts_dev, sizeof(int64_t) * k));
     KM_HIP(hipMalloc(&c->status_dev, sizeof(km::DevStatus)));
@@ -1110,7 +1218,7 @@ int km_set_centroids(km_ctx* c, const double* C, int32_t k, int32_t d) {
             km::diag_env("KM_S1", 1) != 0;
     c->mdelta_geo = (c->path == 2) && !c->fused && !c->s1 && c->g.dp % 32 == 0 && c->g.dp <= 128 &&
                     c->g.k <= 65535 && km::diag_env("KM_MDELTA", 1) != 0;
-    if (c->mdelta_geo) KM_HIP(hipMalloc(&c->stats_full, sizeof(double) * stats_len(c->g)));
+    if (c->mdelta_geo) KM_HIP(hipMalloc(&c->stats_full, sizeof(double) * stats_cap(c->g)));
     if (c->s1) {
       const size_t nt = km::s1_table_entries(c->g);
       KM_HIP(hipMalloc(&c->s1_perm, sizeof(int32_t) * nt));
@@ -1118,7 +1226,7 @@ int km_set_centroids(km_ctx* c, const double* C, int32_t k, int32_t d) {
       KM_HIP(hipMalloc(&c->s1_cn2o, sizeof(float) * kp));
       KM_HIP(hipMalloc(&c->s1_img, sizeof(_Float16) * kp * dp));
       KM_HIP(hipMalloc(&c->s1_cst, sizeof(float) * 8));
-      KM_HIP(hipMalloc(&c->stats_full, sizeof(double) * stats_len(c->g)));
+      KM_HIP(hipMalloc(&c->stats_full, sizeof(double) * stats_cap(c->g)));
       KM_HIP(hipMalloc(&c->chg, sizeof(uint2) * km::s1_chg_entries(c->g, c->n_cu)));
       KM_HIP(hipMalloc(&c->chg_cnt, sizeof(uint32_t) * km::s1_wave_slots(c->n_cu)));
     }
@@ -1160,6 +1268,7 @@ int km_assign_stats(km_ctx* c) {
   KM_HIP(hipSetDevice(c->device));
   int rc = flush_assign(c);
   if (rc != KM_OK) return rc;
+  if (c->w) return run_assign_weighted(c);
   if (fold_ok(c)) {
     // launched by km_update_async together with the update
     if (c->prep_of != c->C64_cur) {
@@ -1180,7 +1289,7 @@ int km_stats_buffer(km_ctx* c, void** p, int64_t* len) {
   }
   c->stats_exported = true;
   *p = c->stats;
-  *len = (int64_t)stats_len(c->g);
+  *len = (int64_t)stats_len(c);
   return KM_OK;
 }
 
@@ -1235,7 +1344,7 @@ int km_update(km_ctx* c, km_status* st, int64_t* counts) {
     ProfScope ps(c, KM_K_UPDATE);
     KM_HIP(km::launch_update(const_cast<double*>(src), c->C64_cur, c->g, c->C64_new, c->work, c->counts_dev, c->qcount,
                              c->ql.nwaves, c->status_dev, c->gate, -1.0, 0, c->stream, 0, nullptr, nullptr,
-                             take_sse_corr(c)));
+                             take_sse_corr(c), wdiv_of(c, src)));
   }
   KM_HIP(hipMemcpyAsync(c->status_host, c->status_dev, sizeof(km::DevStatus), hipMemcpyDeviceToHost, c->stream));
   KM_HIP(hipMemcpyAsync(c->counts_host, c->counts_dev, sizeof(int64_t) * c->g.k, hipMemcpyDeviceToHost, c->stream));
@@ -1354,7 +1463,7 @@ int km_update_async(km_ctx* c, double tol, int64_t empty_seed) {
     // one launch: assign + sums + queued rows + update (last workgroup)
     c->assign_pending = false;
     c->ql = km::QLayout{0, 0};
-    if (!c->stats_clean) KM_HIP(hipMemsetAsync(c->stats, 0, sizeof(double) * stats_len(c->g), c->stream));
+    if (!c->stats_clean) KM_HIP(hipMemsetAsync(c->stats, 0, sizeof(double) * stats_len(c), c->stream));
     km::SmallTail t = small_tail(c);
     t.fold = 1;
     t.old = c->C64_cur;
@@ -1385,7 +1494,8 @@ int km_update_async(km_ctx* c, double tol, int64_t empty_seed) {
     KM_HIP(km::launch_update(one ? c->stats : const_cast<double*>(src), c->C64_cur, c->g, c->C64_new, c->work,
                              c->hist_counts + (size_t)slot * c->g.k, c->qcount, c->ql.nwaves, c->hist + slot,
                              c->gate, tol, repair ? 1 : 0, c->stream, one ? 1 : 0, fold_prep ? c->C32 : nullptr,
-                             fold_prep ? c->cmax : nullptr, take_sse_corr(c)));
+                             fold_prep ? c->cmax : nullptr, take_sse_corr(c),
+                             wdiv_of(c, one ? c->stats : src)));
   }
   if (one) c->stats_clean = true;
   if (repair) {

@@ -45,6 +45,7 @@ class HipEngine:
         self.d = 0
         self.k = 0
         self._stats_t = None
+        self.weighted = False       # load_weights: the stats buffer carries k sums of weights more
         self._tstream = None
         self._coll_ev = None        # [(start, end)] HIP events around each collective while timed
         self.distributed = distributed
@@ -80,13 +81,38 @@ class HipEngine:
         if n:
             self._c(self.lib.km_load_rows(self.ctx, 0, _ptr(rows, _PF), n), "km_load_rows")
         self.n, self.d = n, d
+        self.weighted = False       # km_load_begin released the weights
+        self._stats_t = None        # ... and the centroids with their stats binding
         return n
+
+    def load_weights(self, w) -> None:
+        """This rank's row weights (float64 [n], finite and > 0: the caller
+        validates), or None for none.  Weighted mode: km_assign_stats computes
+        the same labels, then the weighted sums in a second pass over the rows
+        (km_set_weights, kmeans_amd.h)."""
+        was = self.weighted
+        if w is None:
+            self._c(self.lib.km_clear_weights(self.ctx), "km_clear_weights")
+            self.weighted = False
+        else:
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if w.shape != (self.n,):
+                raise ValueError(f"weights of shape {w.shape} for {self.n} local rows")
+            self._c(self.lib.km_set_weights(self.ctx, 0, _ptr(w, _PD), self.n), "km_set_weights")
+            self.weighted = True
+        if was != self.weighted and self._stats_t is not None:
+            # the buffer's length changed and the context dropped the binding
+            self._stats_t = None
+            if self.k:
+                self._bind_stats()
 
     def load_blobs(self, n: int, d: int, global_row0: int, n_centers: int, box: float = 10.0, std: float = 1.0,
                    seed: int = 0) -> int:
         self._c(self.lib.km_generate_blobs(self.ctx, n, d, global_row0, n_centers, box, std, seed),
                 "km_generate_blobs")
         self.n, self.d = n, d
+        self.weighted = False
+        self._stats_t = None
         return n
 
     def sum_x(self) -> np.ndarray:
@@ -118,13 +144,22 @@ class HipEngine:
         C = np.ascontiguousarray(C, dtype=np.float64)
         k, d = C.shape
         self._c(self.lib.km_set_centroids(self.ctx, _ptr(C, _PD), k, d), "km_set_centroids")
-        if self.distributed and (self._stats_t is None or k != self.k):
-            torch = self._torch
-            self._stats_t = torch.zeros(k * (d + 1) + 1, dtype=torch.float64, device=f"cuda:{self.device}")
-            torch.cuda.synchronize(self.device)
-            self._c(self.lib.km_bind_stats_buffer(self.ctx, ctypes.c_void_p(self._stats_t.data_ptr())),
-                    "km_bind_stats_buffer")
+        rebind = self.distributed and (self._stats_t is None or k != self.k)
         self.k = k
+        if rebind:
+            self._bind_stats()
+
+    def stats_len(self) -> int:
+        """Doubles of the stats buffer: [k][d+1] sums and counts, the SSE slot,
+        and with weights the k sums of weights."""
+        return self.k * (self.d + 1) + 1 + (self.k if self.weighted else 0)
+
+    def _bind_stats(self) -> None:
+        torch = self._torch
+        self._stats_t = torch.zeros(self.stats_len(), dtype=torch.float64, device=f"cuda:{self.device}")
+        torch.cuda.synchronize(self.device)
+        self._c(self.lib.km_bind_stats_buffer(self.ctx, ctypes.c_void_p(self._stats_t.data_ptr())),
+                "km_bind_stats_buffer")
 
     def get_centroids(self, which: int = 0) -> np.ndarray:
         out = np.empty((self.k, self.d), dtype=np.float64)

@@ -328,7 +328,9 @@ class KMeans:
     Keyword-only, beyond the reference: init ("random": the reference's
     takeSample of k rows, the default; "k-means||": seeding.py), init_rounds
     (rounds of k-means||), oversampling (its expected picks per round, ell;
-    None = 2 k).
+    None = 2 k).  ``fit`` takes row weights (``sample_weight``, keyword-only):
+    centroids become weighted means, the SSE a weighted sum; labels, cluster
+    sizes and the empty-cluster policy are unchanged.
 
     Compute contract: rows are stored in HBM as float32, rounded once at load
     (a float64 input is not copied at full precision); every row the fit uses
@@ -415,8 +417,27 @@ class KMeans:
             raise ValueError("Data contains NaN or Inf values")
         return centroids
 
+    @staticmethod
+    def _check_weights(sample_weight, n_total: int) -> np.ndarray:
+        """sample_weight as float64 [n_total]: finite and strictly positive (a
+        cluster is then empty exactly when it holds no row)."""
+        w = np.asarray(sample_weight, dtype=np.float64)
+        if w.ndim != 1 or len(w) != n_total:
+            raise ValueError(f"sample_weight has length {len(w) if w.ndim == 1 else w.shape}, "
+                             f"the data has {n_total} rows")
+        if not (np.all(np.isfinite(w)) and np.all(w > 0)):
+            raise ValueError("sample_weight must be finite and positive")
+        return w
+
     # -- public API ----------------------------------------------------------------------
-    def fit(self, rdd, sc=None) -> "KMeans":
+    def fit(self, rdd, sc=None, *, sample_weight=None) -> "KMeans":
+        """``sample_weight``: one weight per row in global row order (every
+        rank passes the whole array), or None.  Labels are unchanged; a
+        cluster's new centroid is sum(w x) / sum(w) over its rows, the SSE
+        sum(w ||x - c||^2); cluster sizes, the empty-cluster policy and
+        ``init="random"`` (takeSample) ignore the weights."""
+        if sample_weight is not None and self.init == "k-means||":
+            raise ValueError("k-means|| with sample_weight is not supported yet")
         if hasattr(rdd, "cache"):
             rdd.cache()                                        # L256
         comm = Communicator()
@@ -425,6 +446,10 @@ class KMeans:
         except EmptyDataset:
             # takeSample of an empty RDD returns [] (L72-74)
             raise ValueError(f"Not enough data points (0) to initialize {self.k} clusters") from None
+        if sample_weight is not None:
+            pl = run.pl
+            w = self._check_weights(sample_weight, pl.n_global)
+            run.engine.load_weights(w[pl.row0:pl.row0 + pl.n_local])
         self._runner, self._runner_src = run, _ref_to(rdd)
         self.centroids = self._initialize_centroids(run)       # L259
         self.sse_history = []                                  # L260

@@ -121,6 +121,34 @@ int km_load_rows(km_ctx* ctx, int64_t row0, const float* rows, int64_t nrows);
 /* Synthetic Gaussian blobs generated in HBM, keyed by global row (benchmarks). */
 int km_generate_blobs(km_ctx* ctx, int64_t n, int32_t d, int64_t global_row0, int32_t n_centers, float box,
                       float stddev, uint64_t seed);
+/* Row weights (fit(..., sample_weight=w); MLlib's weightCol): float64, one
+ * per local row, kept in HBM as float64 (8 bytes per row).  km_set_weights
+ * copies host weights of rows [row0, row0 + nrows) (chunked like
+ * km_load_rows; rows never set weigh 1) and puts the context in weighted
+ * mode; KM_ERR_STATE before km_load_begin and inside a batch.  The caller
+ * guarantees finite, strictly positive weights: with w > 0 a cluster is empty
+ * exactly when it holds no row, so the empty-cluster policy, the device
+ * repair and the reported cluster sizes (row counts) are unchanged.
+ * In weighted mode km_assign_stats computes the same labels (the labels-only
+ * assignment of km_predict, exact on every path) and then runs one weighted
+ * statistics pass over the rows (X is read twice per iteration); delta
+ * statistics, the row gate, the small path's folded update and the k_s1 SSE
+ * correction are off (km_info.delta_stats = 0).  The stats buffer becomes
+ * float64 [k][d+1]: per-cluster sum of w x, then the ROW count; the SSE slot
+ * (sum of w ||x - c_label||^2 with km_set_sse); then k more doubles, the
+ * clusters' sums of weights W.  km_stats_buffer reports the length
+ * k (d+1) + 1 + k and a buffer bound with km_bind_stats_buffer must hold as
+ * many: one sum all-reduce per iteration still suffices.  km_update /
+ * km_update_async divide by W where the row count is positive and keep the
+ * old centroid elsewhere; status, counts, batches and repairs are as without
+ * weights.  km_predict is unaffected.
+ * km_clear_weights returns to unweighted mode (a no-op without weights).
+ * Entering or leaving weighted mode changes the buffer's length: an external
+ * stats buffer is unbound (the context's own is current; bind again).
+ * km_load_begin, km_generate_blobs and km_destroy release the weights.
+ * (Added within ABI 6: new entry points, no existing layout changes.) */
+int km_set_weights(km_ctx* ctx, int64_t row0, const double* w, int64_t nrows);
+int km_clear_weights(km_ctx* ctx);
 /* Local sum_p x_p of the resident rows (float64 [d]; integrity checks). */
 int km_sum_x(km_ctx* ctx, double* out_d);
 /* compute_sse (kmeans_spark.py:38, 278-286): when enabled, km_assign_stats
