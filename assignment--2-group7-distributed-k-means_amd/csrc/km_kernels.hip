@@ -398,7 +398,14 @@ void k_assign_small(const float* __restrict__ X, int64_t n, int d, int k, const 
   // direct-form bound: |D~ - D| <= a*D~ + beta*sqrt(D~) + g0   (DESIGN.md), x2 safety
   const float alpha = 2.0f * (float)(DP + 6 + (2 << b)) * U24;
   const float beta = 2.0f * 2.5f * U24 * cm;
-  const float g0 = 2.0f * 8.0f * U24 * U24 * cm * cm;
+  // ... + underflow: the relative terms hold for normal fp32 results only.  A
+  // square, an fma, the key's index bits or a term of the bound itself that
+  // lands below FLT_MIN is off by up to FLT_MIN (flushed or not): DP
+  // products and sums, the key and the three bound terms, x2.  Rows whose
+  // squared differences underflow (data of magnitude 1e-20 and below: every
+  // score 0) are then ambiguous and go to the float64 queue instead of
+  // taking the lowest index
+  const float g0 = 2.0f * 8.0f * U24 * U24 * cm * cm + 2.0f * (float)(DP + 8) * FLT_MIN;
   const int rep = threadIdx.x & (R - 1);
 
   // rows strided over the grid; the next row is prefetched into registers
