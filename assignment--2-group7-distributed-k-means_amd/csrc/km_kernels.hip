@@ -223,11 +223,17 @@ __device__ __forceinline__ KeyBounds key_bounds(float xn_s, float xabs_s, int dp
 
 // ---------------------------------------------------------------------------
 // Centroid preparation: float64 centroids -> fp32 copy (direct screening),
-// bf16 hi/lo split of -2c (MFMA screening), fp32 ||c||^2, max ||c||.
+// bf16 hi/lo split of -2c (MFMA screening), float64 ||c||^2, max ||c||.
 // Padded rows (k <= j < kp) are zero with ||c||^2 = 1e30 (never selected).
 // ---------------------------------------------------------------------------
+// fp32 upper bound of ||c|| from the float64 ||c||^2.  The root is taken in
+// float64: (float)||c||^2 is denormal or 0 for ||c|| below 1e-19 and inf
+// above 1.8e19, the root of it then no bound at all (1e-30 for 1e-24).  The
+// 1e-30 covers centroids whose norm is itself an fp32 denormal.
+__device__ __forceinline__ float cnorm_bound(double nn) { return (float)sqrt(nn) * 1.0001f + 1e-30f; }
+
 __global__ __launch_bounds__(64) void k_prep_centroids(const double* __restrict__ C64, int k, int d, int dp,
-                                                       float* __restrict__ C32, float* __restrict__ cn2,
+                                                       float* __restrict__ C32, double* __restrict__ cn2,
                                                        float* __restrict__ cmax, float* __restrict__ cabs,
                                                        double* __restrict__ C64T, double* __restrict__ C64P, const int* __restrict__ gate) {
   if (*gate) return;  // a stopped batch (km_update_async): the rest of it is a no-op
@@ -252,9 +258,9 @@ __global__ __launch_bounds__(64) void k_prep_centroids(const double* __restrict_
   }
   if (lane == 0 && j < k) atomicMax((unsigned int*)cabs, __float_as_uint(am));
   if (lane == 0) {
-    cn2[j] = (j < k) ? (float)nn : 1e30f;
+    cn2[j] = (j < k) ? nn : 1e30;
     if (j < k) {
-      const float cn = sqrtf((float)nn) * 1.0001f + 1e-30f;
+      const float cn = cnorm_bound(nn);
       atomicMax((unsigned int*)cmax, __float_as_uint(cn));
     }
   }
@@ -279,7 +285,7 @@ __global__ __launch_bounds__(256) void k_prep_small(const double* __restrict__ C
     }
     nn = wave_sum(nn);
     if (lane == 0 && j < k) {
-      const float cn = sqrtf((float)nn) * 1.0001f + 1e-30f;
+      const float cn = cnorm_bound(nn);
       mx = max(mx, __float_as_uint(cn));
     }
   }
@@ -302,7 +308,7 @@ __global__ void k_zero_maxima(float* __restrict__ cmax, float* __restrict__ cabs
   }
 }
 
-hipError_t launch_prep_centroids(const double* C64, const Geometry& g, float* C32, float* cn2, float* cmax,
+hipError_t launch_prep_centroids(const double* C64, const Geometry& g, float* C32, double* cn2, float* cmax,
                                  float* cabs, double* C64T, double* C64P, const int* gate, hipStream_t s) {
   // the two maxima are zeroed by a gated kernel (a memset would run in a
   // stopped batch and leave the live images' bound inputs at zero)
@@ -791,7 +797,7 @@ __device__ __forceinline__ float mfma_scale(float xabs, float cabs) {
 }
 
 __global__ __launch_bounds__(64) void k_prep_split(const float* __restrict__ C32, int kp, int dp,
-                                                   const float* __restrict__ cn2, const float* __restrict__ xabs,
+                                                   const double* __restrict__ cn2, const float* __restrict__ xabs,
                                                    const float* __restrict__ cabs, _Float16* __restrict__ Chi,
                                                    _Float16* __restrict__ Clo, float* __restrict__ cn2s, int k, const int* __restrict__ gate) {
   if (*gate) return;  // a stopped batch (km_update_async): the rest of it is a no-op
@@ -803,7 +809,10 @@ __global__ __launch_bounds__(64) void k_prep_split(const float* __restrict__ C32
     Chi[(size_t)j * dp + f] = hi;
     Clo[(size_t)j * dp + f] = (_Float16)(m2 - (float)hi);
   }
-  if (threadIdx.x == 0) cn2s[j] = (j < k) ? cn2[j] * s * s : 1e30f;
+  // the accumulator seed ||c||^2 s^2: the float64 norm scaled, then rounded
+  // once (as k_s1_prep does).  An fp32 ||c||^2 would be denormal, 0 or inf
+  // before the scale brings it into range
+  if (threadIdx.x == 0) cn2s[j] = (j < k) ? (float)(cn2[j] * (double)s * (double)s) : 1e30f;
 }
 
 // top-3 insert carrying the index of the two best (a candidate equal to a
@@ -2072,7 +2081,7 @@ bool mfma_path_ok(const Geometry& g) {
   }
 }
 
-hipError_t launch_prep_split(const float* C32, const Geometry& g, const float* cn2, const float* xabs,
+hipError_t launch_prep_split(const float* C32, const Geometry& g, const double* cn2, const float* xabs,
                              const float* cabs, _Float16* Chi, _Float16* Clo, float* cn2s, const int* gate, hipStream_t s) {
   hipLaunchKernelGGL(k_prep_split, dim3(g.kp), dim3(64), 0, s, C32, g.kp, g.dp, cn2, xabs, cabs, Chi, Clo, cn2s,
                      g.k, gate);
@@ -5056,7 +5065,7 @@ __device__ void update_one_body(double* __restrict__ stats, const double* __rest
       mx = fmax(mx, sh);
       nf |= (nfl != 0.0);
       emp += (cnt == 0.0);
-      if (C32) cmb = max(cmb, __float_as_uint(sqrtf((float)nn) * 1.0001f + 1e-30f));
+      if (C32) cmb = max(cmb, __float_as_uint(cnorm_bound(nn)));
     }
   }
   if (C32)  // padded rows k <= j < kp stay zero (as k_prep_small writes them)

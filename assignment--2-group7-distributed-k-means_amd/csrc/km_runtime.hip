@@ -174,7 +174,7 @@ struct km_ctx {
   float* C32 = nullptr;
   _Float16* Chi = nullptr;  // fp16 hi/lo of -2*c*s [kp][dp]
   _Float16* Clo = nullptr;
-  float* cn2 = nullptr;      // ||c||^2 (fp32)
+  double* cn2 = nullptr;     // ||c||^2 (float64; k_prep_split scales, then rounds)
   float* cn2s = nullptr;     // ||c||^2 s^2, pads 1e30
   float* cmax = nullptr;     // max ||c||
   float* cabs = nullptr;     // max |c_f|
@@ -1184,7 +1184,7 @@ int km_set_centroids(km_ctx* c, const double* C, int32_t k, int32_t d) {
     KM_HIP(hipMalloc(&c->C32, sizeof(float) * kp * dp));
     KM_HIP(hipMalloc(&c->Chi, sizeof(_Float16) * kp * dp));
     KM_HIP(hipMalloc(&c->Clo, sizeof(_Float16) * kp * dp));
-    KM_HIP(hipMalloc(&c->cn2, sizeof(float) * kp));
+    KM_HIP(hipMalloc(&c->cn2, sizeof(double) * kp));
     KM_HIP(hipMalloc(&c->cn2s, sizeof(float) * kp));
     KM_HIP(hipMalloc(&c->ChiF, sizeof(_Float16) * kp * dp));
     KM_HIP(hipMalloc(&c->CloF, sizeof(_Float16) * kp * dp));

@@ -336,18 +336,22 @@ __global__ __launch_bounds__(64) void k_s1_prep(const double* __restrict__ C64, 
     // rounding of s^2 ||c||^2, the 16x16x32 accumulation model (per MFMA 4
     // roundings of a partial sum and 28 u of the largest product; ns2 MFMAs
     // per key), fp16 underflow; times 1.25
-    const float cm = *cmax, ca = *cabs * (1.0f + U24), xa = *xabs;
-    const float s2 = s * s, sq = sqrtf((float)dp) * 1.0001f, nm = (float)sg.ns2;
-    const float e1 = 1.25f * (2.0f * s2 * cm * (2.0f * U16 + U16 * U16 + 2.0f * U24) +
-                              nm * 4.0f * U24 * 2.0f * s2 * cm * (1.0f + 2.0f * U16) +
+    // Every product is formed from scaled factors (s cm, s ca, s xa: below
+    // 2^14 sqrt(dp)): s^2 on its own overflows for data below 2^-50 and
+    // underflows above 2^77, and the bound was then inf (every row queued)
+    // or 0
+    const float cm = *cmax * s, ca = *cabs * (1.0f + U24) * s, xa = *xabs * s;
+    const float sq = sqrtf((float)dp) * 1.0001f, nm = (float)sg.ns2;
+    const float e1 = 1.25f * (2.0f * s * cm * (2.0f * U16 + U16 * U16 + 2.0f * U24) +
+                              nm * 4.0f * U24 * 2.0f * s * cm * (1.0f + 2.0f * U16) +
                               ldexpf(1.0f, -25) * s * sq * (1.0f + U16));
-    const float e0 = 1.25f * (U24 * s2 * cm * cm + nm * (4.0f * U24 * s2 * cm * cm +
-                                                          28.0f * U24 * 2.0f * s2 * ca * xa * (1.0f + U16) * (1.0f + U16)) +
-                              ldexpf(1.0f, -24) * s * sq * cm);
+    const float e0 = 1.25f * (U24 * cm * cm + nm * (4.0f * U24 * cm * cm +
+                                                     28.0f * U24 * 2.0f * ca * xa * (1.0f + U16) * (1.0f + U16)) +
+                              ldexpf(1.0f, -24) * sq * cm);
     cst[0] = s;
     cst[1] = e1 * 1.0001f;
     cst[2] = e0 * 1.0001f + 1e-30f;
-    cst[3] = U24 * cm * 1.01f + 1e-37f;  // g: ||c - c'|| <= u ||c||
+    cst[3] = U24 * *cmax * 1.01f + 1e-37f;  // g: ||c - c'|| <= u ||c|| (unscaled)
   }
 }
 
@@ -652,7 +656,7 @@ __global__ __launch_bounds__(s1_waves(NS2, NB) * 64, s1_waves(NS2, NB) / 4) void
     if (l1 >= 0) {
       if (Lo > U1)
         kd = 0u;
-      else if (cnt == 2u && l2 >= 0)
+      else if (cnt == 2u && l2 >= 0 && s2 != s1)  // (s2 == s1: both Dt overflowed, no bound took a slot)
         kd = 1u;
     }
     if (act0) {

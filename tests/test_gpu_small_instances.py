@@ -47,18 +47,23 @@ def _dp(d):
     return (d + 15) // 16 * 16
 
 
-def _load(X, C0, sse, path=1, dp=None, kp=None):
+def _load(X, C0, sse, path=1, dp=None, kp=None, fused=None, screen=None):
     """An engine holding X and C0; the dispatch is asserted first, so that a
-    change of it cannot hide the kernel from the test."""
+    change of it cannot hide the kernel from the test.  screen: km_set_screen
+    mode forced before the centroids are set (path 2)."""
     eng = _engine()
     eng.load_host(X.astype(np.float32))
     eng.set_sse(sse)
+    if screen is not None:
+        eng.set_screen(screen)
     eng.set_centroids(C0)
     info = eng.info()
     assert info["path"] == path, info
     assert info["dp"] == (_dp(X.shape[1]) if dp is None else dp), info
     if kp is not None:
         assert info["kp"] == kp, info
+    if fused is not None:
+        assert info["fused_stats"] == fused, info
     return eng
 
 
@@ -117,9 +122,11 @@ def _reference(key, X, C0):
     return _refs[key]
 
 
-def _check_step(out, ref, sse):
+def _check_step(out, ref, sse, atol=0.0):
     """Labels and counts exact, sums, centroids and SSE to 1e-9 relative; the
-    second sweep identical in labels and counts, its sums within 1e-12."""
+    second sweep identical in labels and counts, its sums within 1e-12.
+    atol: absolute slack of the sums and centroids, for inputs whose sums
+    cancel (noise around the origin)."""
     k, d = ref["sums"].shape
     d1 = d + 1
     first = None
@@ -130,7 +137,7 @@ def _check_step(out, ref, sse):
         with np.errstate(divide="ignore", invalid="ignore"):
             rel = np.nanmax(np.where(ref["sums"] != 0, np.abs(tab[:, :d] / ref["sums"] - 1), 0.0))
         print(f"sums: max rel err {rel:.3e}; sse {flat[-1]!r} vs {ref['sse_fit']!r}")
-        np.testing.assert_allclose(tab[:, :d], ref["sums"], rtol=1e-9, atol=0)
+        np.testing.assert_allclose(tab[:, :d], ref["sums"], rtol=1e-9, atol=atol)
         if sse:
             np.testing.assert_allclose(flat[-1], ref["sse_fit"], rtol=1e-9)
             np.testing.assert_allclose(flat[-1], ref["sse"], rtol=1e-9)
@@ -140,10 +147,10 @@ def _check_step(out, ref, sse):
             first = tab
         else:
             np.testing.assert_array_equal(tab[:, d], first[:, d])
-            np.testing.assert_allclose(tab[:, :d], first[:, :d], rtol=1e-12, atol=0)
+            np.testing.assert_allclose(tab[:, :d], first[:, :d], rtol=1e-12, atol=atol)
     np.testing.assert_array_equal(out["counts"], ref["counts"])
     assert out["n_empty"] == int((ref["counts"] == 0).sum()) and out["nonfinite"] == 0
-    np.testing.assert_allclose(out["new"], ref["new"], rtol=1e-9, atol=0)
+    np.testing.assert_allclose(out["new"], ref["new"], rtol=1e-9, atol=atol)
     if sse:
         np.testing.assert_allclose(out["sse"], ref["sse_fit"], rtol=1e-9)
 
