@@ -66,6 +66,7 @@ SIGNATURES = {
     "km_sync": [_P],
     "km_info_get": [_P, ctypes.POINTER(KmInfo)],
     "km_gated_rows": [_P, _PI64],
+    "km_stats_route": [_P, _PI32, _PI32, _PI32, _PI32, _PI32],
     "km_load_begin": [_P, _I64, _I32],
     "km_load_rows": [_P, _I64, _PF, _I64],
     "km_generate_blobs": [_P, _I64, _I32, _I64, _I32, ctypes.c_float, ctypes.c_float, ctypes.c_uint64],

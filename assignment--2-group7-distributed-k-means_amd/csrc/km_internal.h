@@ -181,6 +181,12 @@ hipError_t launch_row_norm(const float* X, const Geometry& g, float* xnorm, hipS
 // large k: counting sort of the labels + per-cluster float64 row sums (X read
 // once); scratch = sorted_stats_words(n, k) uint32 words
 bool stats_needs_sort(const Geometry& g);
+// the split of the range-tiled statistics table (k_stats / k_wstats): fr
+// features and kr clusters per workgroup; extra = table slots of a cluster
+// beside its features (1: the count; weighted 2: sum of weights and count).
+// The launchers, stats_needs_sort / wstats_needs_sort and km_stats_route all
+// read it from here
+void stats_ranges(const Geometry& g, int* fr_out, int* kr_out, int extra = 1);
 size_t sorted_stats_words(int64_t n, int k);
 // C64P != nullptr: the SSE residuals are accumulated in the same pass
 hipError_t launch_stats_sorted(const float* X, const Geometry& g, const int32_t* labels, double* stats,

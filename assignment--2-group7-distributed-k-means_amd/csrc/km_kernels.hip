@@ -4205,7 +4205,7 @@ __global__ __launch_bounds__(1024) void k_stats(const float* __restrict__ X, int
 // those needing the fewest cluster ranges; segments stay >= 64 bytes
 // extra: table slots of a cluster beside its fr features (1: the count;
 // weighted statistics 2: the sum of weights and the count)
-static void stats_ranges(const Geometry& g, int* fr_out, int* kr_out, int extra = 1) {
+void stats_ranges(const Geometry& g, int* fr_out, int* kr_out, int extra) {
   int best_fr = g.dp, best_kr = 0, best_ncr = 1 << 30;
   if (g.dp > 256) {
     // wide rows: any multiple of 4 dividing dp, at most 256 (dp = 2000: 80)
@@ -4546,6 +4546,7 @@ __global__ __launch_bounds__(1024) void k_scan(const uint32_t* __restrict__ cnt,
 // wave of the chip on the same few words at the memory side.
 static constexpr int SCAT_THREADS = 1024, SCAT_ROWS = 8;
 static constexpr int SCAT_PER = SCAT_THREADS * SCAT_ROWS;  // rows per workgroup
+static constexpr size_t SORT_LDS = 64 * 1024;  // k_hist / k_scatter: their per-cluster counters, 4 bytes each
 
 __global__ __launch_bounds__(SCAT_THREADS) void k_scatter(const int32_t* __restrict__ labels, int64_t n, int k,
                                                           uint32_t* __restrict__ cur, uint32_t* __restrict__ perm,
@@ -4788,6 +4789,11 @@ __global__ __launch_bounds__(256) void k_wsegsum(const float* __restrict__ X, in
 
 size_t sorted_stats_words(int64_t n, int k) { return 2 * (size_t)n + 3 * (size_t)k + 64; }
 
+// k_hist and k_scatter keep one 32-bit counter per cluster in LDS, 64 KiB of
+// it: past 16384 clusters the sort cannot run (stats_sorted refuses), and the
+// range-tiled table takes the statistics however many ranges it needs
+static bool sort_fits(const Geometry& g) { return (size_t)g.k * 4 <= SORT_LDS; }
+
 // the range-tiled k_stats reads X once per LDS-sized cluster range; from three
 // ranges on, the sort (one gathered read of X plus ~5 bytes per row of
 // label/permutation traffic, and cursor atomics that contend when k is small)
@@ -4795,6 +4801,7 @@ size_t sorted_stats_words(int64_t n, int k) { return 2 * (size_t)n + 3 * (size_t
 bool stats_needs_sort(const Geometry& g) {
   static const int min_ranges = diag_env("KM_SORT_MIN_RANGES", 3);  // A/B knob
   if (g.dp > 256) return false;  // k_segsum holds a row in one wave-instruction
+  if (!sort_fits(g)) return false;
   int fr = 0, kr = 0;
   stats_ranges(g, &fr, &kr);
   return kr == 0 || (g.k + kr - 1) / kr >= min_ranges;
@@ -4815,7 +4822,7 @@ static hipError_t stats_sorted(const float* X, const Geometry& g, const int32_t*
   int64_t hb = (g.n + 1023) / 1024;
   if (hb > n_cu * 2) hb = n_cu * 2;
   const size_t hist_lds = (size_t)g.k * 4;
-  if (hist_lds > 64 * 1024) return hipErrorInvalidValue;  // k <= 16384
+  if (hist_lds > SORT_LDS) return hipErrorInvalidValue;  // k <= 16384 (sort_fits)
   hipLaunchKernelGGL(k_hist, dim3((unsigned)hb), dim3(1024), hist_lds, s, labels, g.n, g.k, cnt, gate);
   hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, cnt, g.k, off, cur, gate);
   const int64_t sb = (g.n + SCAT_PER - 1) / SCAT_PER;
@@ -4861,7 +4868,7 @@ hipError_t launch_stats_sorted(const float* X, const Geometry& g, const int32_t*
 
 // the weighted statistics' table row has one slot more (stats_ranges extra = 2)
 bool wstats_needs_sort(const Geometry& g) {
-  if (g.dp > 256) return false;
+  if (g.dp > 256 || !sort_fits(g)) return false;
   int fr = 0, kr = 0;
   stats_ranges(g, &fr, &kr, 2);
   return kr == 0 || (g.k + kr - 1) / kr >= 3;

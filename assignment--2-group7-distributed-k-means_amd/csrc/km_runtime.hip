@@ -554,6 +554,15 @@ bool use_s1(km_ctx* c, bool with_stats) {
   return !with_stats || (c->delta_ready && !c->stats_exported && km::s1_delta_ok(c->g, c->n_cu));
 }
 
+// the statistics pass of a full-statistics km_assign_stats (km_stats_route):
+// 0 inside the assign kernel, 1 the range-tiled table, 2 the counting sort.
+// run_assign and run_assign_weighted choose their pass by it
+int stats_route(const km_ctx* c) {
+  if (c->w) return km::wstats_needs_sort(c->g) ? 2 : 1;
+  if (c->path == 1 || c->fused) return 0;
+  return km::stats_needs_sort(c->g) ? 2 : 1;
+}
+
 // before an update reads the statistics: delta -> fold into the full sums;
 // full -> keep them as the base of the next deltas.  Returns the buffer the
 // update reads: with `clear` (an update that leaves its input alone) the
@@ -780,7 +789,7 @@ int run_assign(km_ctx* c, bool with_stats) {
   }
   if (with_stats) {
     ProfScope ps(c, KM_K_STATS);
-    if (km::stats_needs_sort(g)) {
+    if (stats_route(c) == 2) {
       const size_t words = km::sorted_stats_words(g.n, g.k);
       if (words > c->sort_words) {
         dfree(c->sort_scratch);
@@ -815,7 +824,7 @@ int run_assign_weighted(km_ctx* c) {
   c->stats_clean = false;
   const bool sse = c->want_sse;
   ProfScope ps(c, KM_K_STATS);
-  if (km::wstats_needs_sort(g)) {
+  if (stats_route(c) == 2) {
     const size_t words = km::sorted_stats_words(g.n, g.k);
     if (words > c->sort_words) {
       dfree(c->sort_scratch);
@@ -966,6 +975,23 @@ int km_gated_rows(km_ctx* c, int64_t* out) {
   int64_t total = 0;
   for (uint32_t v : cnt) total += v;
   *out = total;
+  return KM_OK;
+}
+
+int km_stats_route(km_ctx* c, int32_t* route, int32_t* cluster_ranges, int32_t* kr, int32_t* feature_ranges,
+                   int32_t* fr) {
+  KM_REQUIRE(c && route && cluster_ranges && kr && feature_ranges && fr, KM_ERR_ARG, "km_stats_route: null arg");
+  KM_REQUIRE(c->have_c && c->path != 0, KM_ERR_STATE, "km_stats_route: set centroids of a supported geometry first");
+  *route = stats_route(c);
+  *cluster_ranges = *kr = *feature_ranges = *fr = 0;
+  if (*route == 0) return KM_OK;
+  int f = 0, r = 0;
+  km::stats_ranges(c->g, &f, &r, c->w ? 2 : 1);
+  KM_REQUIRE(f > 0 && r > 0, KM_ERR_UNSUPPORTED, "km_stats_route: no table split for this geometry");
+  *fr = f;
+  *kr = r;
+  *feature_ranges = c->g.dp / f;
+  *cluster_ranges = (c->g.k + r - 1) / r;
   return KM_OK;
 }
 

@@ -369,6 +369,13 @@ class HipEngine:
         rows = ctypes.c_int64(-1)
         self._c(self.lib.km_gated_rows(self.ctx, ctypes.byref(rows)), "km_gated_rows")
         out["gated_rows"] = rows.value
+        # the statistics pass of the next full-statistics assign (km_stats_route):
+        # 0 in the assign kernel, 1 range-tiled table, 2 counting sort; and the table's split
+        # (absent before the first set_centroids and for a geometry without kernels)
+        v = [ctypes.c_int32() for _ in range(5)]
+        if self.lib.km_stats_route(self.ctx, *[ctypes.byref(x) for x in v]) == 0:
+            for key, x in zip(("stats_route", "stats_cluster_ranges", "stats_kr", "stats_feature_ranges", "stats_fr"), v):
+                out[key] = x.value
         return out
 
     # -- profiling ---------------------------------------------------------------

@@ -111,6 +111,20 @@ int km_info_get(km_ctx* ctx, km_info* out);
  * gated.  Synchronises the stream.  (Added within ABI 6: a new entry point,
  * no existing layout changes.) */
 int km_gated_rows(km_ctx* ctx, int64_t* out);
+/* Which statistics pass the next km_assign_stats with FULL statistics runs
+ * for the current geometry and weight mode (read-only; needs centroids):
+ *   *route = 0  inside the assign kernel (small path, fused path);
+ *            1  the range-tiled LDS table (k_stats; weighted k_wstats);
+ *            2  the counting sort and segment sums (k_segsum / k_wsegsum).
+ * For routes 1 and 2 the split of the table: *fr features and *kr clusters
+ * per workgroup, *feature_ranges = dp / fr and *cluster_ranges =
+ * ceil(k / kr) of them (route 2 sorts because the table would need that
+ * many cluster ranges); all four are 0 for route 0.  A delta-statistics pass
+ * (km_info.delta_stats) folds its change list instead and is not described.
+ * The values are the ones the dispatch itself reads, not a second
+ * computation.  (Added within ABI 6: a new entry point, no layout changes.) */
+int km_stats_route(km_ctx* ctx, int32_t* route, int32_t* cluster_ranges, int32_t* kr, int32_t* feature_ranges,
+                   int32_t* fr);
 
 /* Materialise this rank's rows in HBM once: replaces sc.parallelize(X) +
  * rdd.cache() (kmeans_spark.py:256, 369, 418, 471, 518, 568).  km_load_begin

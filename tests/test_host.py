@@ -37,6 +37,19 @@ def test_library_exports_every_header_symbol():
     assert lib.km_abi_version() == 6
 
 
+def test_stats_route_is_bound_and_checks_its_arguments():
+    # km_stats_route (added within ABI 6): five int32 outputs; a null context
+    # is an argument error before anything touches a device
+    import ctypes
+    from kmeans_amd import _lib
+    lib = _lib.load()
+    assert len(_lib.SIGNATURES["km_stats_route"]) == 6
+    out = [ctypes.c_int32(-7) for _ in range(5)]
+    assert lib.km_stats_route(None, *[ctypes.byref(v) for v in out]) == -1   # KM_ERR_ARG
+    assert b"km_stats_route" in lib.km_last_error()
+    assert [v.value for v in out] == [-7] * 5
+
+
 def test_product_library_has_no_diagnostic_kernels():
     # the environment knobs exist only in the diagnostic build (make diag,
     # -DKM_DIAG); the timing-ablation variants of round 1-5 are gone (round 6)
