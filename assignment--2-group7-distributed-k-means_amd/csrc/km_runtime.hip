@@ -460,6 +460,22 @@ void free_repair(km_ctx* c) {
   c->rep_k = 0;
 }
 
+// the takeSample layout and everything sized by it: a layout belongs to the
+// rows it was set for (km_set_layout installs a new one, km_load_begin ends it)
+void drop_layout(km_ctx* c) {
+  free_repair(c);
+  dfree(c->rep_sizes);
+  dfree(c->rep_bases);
+  c->rep_enabled = false;
+  c->rep_armed = false;
+  c->rep_wait = false;
+  c->rep_mode = 0;
+  c->rep_nparts = 0;
+  c->rep_total = 0;
+  c->rep_maxpart = 0;
+  c->rep_row0 = 0;
+}
+
 // takeSample's fraction for num rows of total (sampling.py _fraction)
 double sample_fraction(int64_t num, int64_t total) {
   const double fraction = (double)num / (double)total;
@@ -1008,6 +1024,7 @@ int km_load_begin(km_ctx* c, int64_t n, int32_t d) {
   KM_HIP(hipStreamSynchronize(c->stream));
   free_data(c);
   free_centroids(c);
+  drop_layout(c);  // the takeSample layout described the rows just released
   c->g = km::Geometry{};
   c->g.n = n;
   c->g.d = d;
@@ -1408,13 +1425,8 @@ int km_set_layout(km_ctx* c, const int64_t* sizes, int32_t nparts, int64_t row0,
     if (rcf != KM_OK) return rcf;
   }
   KM_HIP(hipStreamSynchronize(c->stream));
-  free_repair(c);
-  dfree(c->rep_sizes);
-  dfree(c->rep_bases);
-  c->rep_enabled = false;
+  drop_layout(c);
   c->rep_nparts = nparts;
-  c->rep_total = 0;
-  c->rep_maxpart = 0;
   c->rep_row0 = row0;
   std::vector<int64_t> bases(nparts);
   for (int i = 0; i < nparts; ++i) {

@@ -47,6 +47,7 @@ class HipEngine:
         self._stats_t = None
         self.weighted = False       # load_weights: the stats buffer carries k sums of weights more
         self._tstream = None
+        self._rep_mode, self._rep_t = 0, None   # set_layout; a load ends the layout
         self._coll_ev = None        # [(start, end)] HIP events around each collective while timed
         self.distributed = distributed
         if distributed:
@@ -83,6 +84,7 @@ class HipEngine:
         self.n, self.d = n, d
         self.weighted = False       # km_load_begin released the weights
         self._stats_t = None        # ... and the centroids with their stats binding
+        self._rep_mode, self._rep_t = 0, None   # ... and the takeSample layout (set_layout again)
         return n
 
     def load_weights(self, w) -> None:
@@ -113,6 +115,7 @@ class HipEngine:
         self.n, self.d = n, d
         self.weighted = False
         self._stats_t = None
+        self._rep_mode, self._rep_t = 0, None
         return n
 
     def sum_x(self) -> np.ndarray:

@@ -220,7 +220,10 @@ int km_update(km_ctx* ctx, km_status* st, int64_t* counts);
  * max_shift, without stopping the batch (km_status.repaired = 1).  Otherwise
  * (or if a pass overflows its slots or comes back short: the device does not
  * retry PySpark's resampling loop) empty clusters stop the batch and the
- * caller repairs them on the host with the same policy. */
+ * caller repairs them on the host with the same policy.
+ * The layout belongs to the loaded rows: km_load_begin (and with it
+ * km_generate_blobs) ends it, with the device repair and its buffers, as a
+ * new km_set_layout does; set it again after every load. */
 int km_set_layout(km_ctx* ctx, const int64_t* sizes, int32_t nparts, int64_t row0, int32_t device_repair);
 /* device_repair = 2 (ABI 4): the rows are spread over ranks, this context
  * holding global rows [row0, row0 + n).  Every rank runs the same takeSample
