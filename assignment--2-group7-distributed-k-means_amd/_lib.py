@@ -15,8 +15,11 @@ import threading
 HERE = os.path.dirname(os.path.abspath(__file__))
 # KM_LIB: another build of the same sources (the diagnostic library, or an A/B
 # variant from `make alt`), selected per process instead of copied over the
-# product file (scripts/gpu_ab.sh)
-LIB_PATH = os.environ.get("KM_LIB") or os.path.join(HERE, "libkmeans_amd.so")
+# product file (scripts/gpu_ab.sh).  KM_LIB=diag is the test suite's name for
+# the diagnostic library (tests/conftest.py replaces the file name and keeps
+# the directory, so the default must carry the package directory)
+_KM_LIB = os.environ.get("KM_LIB")
+LIB_PATH = os.path.join(HERE, "libkmeans_amd.so") if _KM_LIB in (None, "", "diag") else _KM_LIB
 ROOT = os.path.dirname(HERE)
 HEADER = os.path.join(ROOT, "include", "kmeans_amd.h")
 

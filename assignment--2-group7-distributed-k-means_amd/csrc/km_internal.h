@@ -180,38 +180,32 @@ bool fused16_ok(const Geometry& g);
 hipError_t launch_row_norm(const float* X, const Geometry& g, float* xnorm, hipStream_t s);
 // large k: counting sort of the labels + per-cluster float64 row sums (X read
 // once); scratch = sorted_stats_words(n, k) uint32 words
-bool stats_needs_sort(const Geometry& g);
-// the split of the range-tiled statistics table (k_stats / k_wstats): fr
-// features and kr clusters per workgroup; extra = table slots of a cluster
-// beside its features (1: the count; weighted 2: sum of weights and count).
-// The launchers, stats_needs_sort / wstats_needs_sort and km_stats_route all
-// read it from here
-void stats_ranges(const Geometry& g, int* fr_out, int* kr_out, int extra = 1);
+// extra: as stats_ranges
+bool stats_needs_sort(const Geometry& g, int extra);
+// the split of the range-tiled statistics table (k_stats): fr features and kr
+// clusters per workgroup; extra = table slots of a cluster beside its
+// features (1: the count; weighted 2: sum of weights and count).  The
+// launchers, stats_needs_sort and km_stats_route all read it from here
+void stats_ranges(const Geometry& g, int* fr_out, int* kr_out, int extra);
 size_t sorted_stats_words(int64_t n, int k);
-// C64P != nullptr: the SSE residuals are accumulated in the same pass
-hipError_t launch_stats_sorted(const float* X, const Geometry& g, const int32_t* labels, double* stats,
-                               uint32_t* scratch, const double* C64P, int n_cu, const int* gate, hipStream_t s);
-// C64P != nullptr: the SSE residuals are accumulated in the same pass
-// C64P, C32 != nullptr: the SSE residuals in the same pass (to the fp32 image,
-// corrected per cluster to the float64 centroid at the flush)
-hipError_t launch_stats(const float* X, const Geometry& g, const int32_t* labels, double* stats, int n_cu,
-                        const int* gate, hipStream_t s, const double* C64P = nullptr, const float* C32 = nullptr);
-// Weighted statistics (km_set_weights; fit(..., sample_weight=w)): labels in
-// place, one read of X.  stats = [k][d+1] weighted sums sum w x and ROW
-// counts, the SSE slot (sum w ||x - c||^2 with the float64 centroids C64 of
-// row stride c64s -- C64P and dp, or the small path's [k][d] -- and C32),
-// then wsum[k] = sum w per cluster at stats + k (d+1) + 1 (the update's
-// divisor).  launch_wstats: the k_stats scheme (LDS table, feature ranges,
-// wide rows); launch_wstats_sorted: the counting sort and weighted segment
-// sums where the table does not fit (wstats_needs_sort; scratch as
-// launch_stats_sorted)
-bool wstats_needs_sort(const Geometry& g);
-hipError_t launch_wstats(const float* X, const Geometry& g, const int32_t* labels, const double* w, double* stats,
-                         int n_cu, const int* gate, hipStream_t s, const double* C64 = nullptr, int c64s = 0,
-                         const float* C32 = nullptr);
-hipError_t launch_wstats_sorted(const float* X, const Geometry& g, const int32_t* labels, const double* w,
-                                double* stats, uint32_t* scratch, const double* C64P, int n_cu, const int* gate,
-                                hipStream_t s);
+// The two statistics routes, labels in place, one read of X.  launch_stats:
+// the LDS table (feature ranges, wide rows); launch_stats_sorted: the
+// counting sort and segment sums where the table does not fit
+// (stats_needs_sort).
+// w == nullptr: stats = [k][d+1] sums and row counts.
+// w != nullptr (km_set_weights; fit(..., sample_weight=w)): weighted sums
+// sum w x and ROW counts, and wsum[k] = sum w per cluster at
+// stats + k (d+1) + 1 (the update's divisor).
+// SSE residuals (sum ||x - c||^2, weighted sum w ||x - c||^2) into the SSE
+// slot in the same pass: launch_stats with C64, C32 != nullptr (to the fp32
+// image, corrected per cluster to the float64 centroid at the flush; C64 has
+// row stride c64s -- C64P and dp, or the small path's [k][d], weighted only);
+// launch_stats_sorted with C64P != nullptr.
+hipError_t launch_stats(const float* X, const Geometry& g, const int32_t* labels, const double* w, double* stats,
+                        int n_cu, const int* gate, hipStream_t s, const double* C64, int c64s, const float* C32);
+hipError_t launch_stats_sorted(const float* X, const Geometry& g, const int32_t* labels, const double* w,
+                               double* stats, uint32_t* scratch, const double* C64P, int n_cu, const int* gate,
+                               hipStream_t s);
 // stats = [k][d+1] sums and counts, then the SSE slot stats[k (d+1)]
 // gate: the batch's stop flag (kernels of later iterations no-op once it is
 // set); stop_tol >= 0 lets k_finalize raise it (KM_STOP_*), < 0 never

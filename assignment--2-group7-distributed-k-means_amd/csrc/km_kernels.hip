@@ -356,17 +356,9 @@ __device__ void update_one_body(double* __restrict__ stats, const double* __rest
 // A/B knobs, c2 on one MI355X (profiles/r5_c2_small_ab.json):
 //   KM_SMALL_SERP serpentine sweep: 153-155 -> 145 us (6,450 -> 6,840 it/s)
 //   KM_SMALL_SC   centroids as scalar operands: 141-142 -> 135-136 us
-//   KM_SMALL_PF2  two rows prefetched (4 waves): +4-5 us, off
-//   KM_SMALL_PF8  the one-row prefetch at 6 waves per SIMD: +5 us, off
 //   KM_SMALL_NTL  non-temporal label stores: -1 us; 32 statistics replicas +5 us
-#ifndef KM_SMALL_PF2
-#define KM_SMALL_PF2 0
-#endif
 #ifndef KM_SMALL_SC
 #define KM_SMALL_SC 1
-#endif
-#ifndef KM_SMALL_PF8
-#define KM_SMALL_PF8 0
 #endif
 #ifndef KM_SMALL_SERP
 #define KM_SMALL_SERP 1
@@ -423,24 +415,15 @@ void k_assign_small(const float* __restrict__ X, int64_t n, int d, int k, const 
   uint32_t* wq = reinterpret_cast<uint32_t*>(smem + ((k * DP * 4 + 15) / 16) * 16 + (fuse ? (size_t)k * d1 * R * 8 : 0)) +
                  (threadIdx.x >> 6) * SMALL_QW;
   uint32_t wq_n = 0;
-  // PF: the next row prefetched into registers while this one is processed
-  // (at 8 waves per SIMD the other waves hide the latency instead: no
-  // prefetch, 2 dp fewer VGPRs); PF2: two rows ahead (KM_SMALL_PF2)
-  constexpr bool PF = WPE < 8 || KM_SMALL_PF8;
-  constexpr bool PF2 = PF && KM_SMALL_PF2 && DP <= 16;
   // serpentine sweep: every other launch visits the rows from the last one
   // down, so its first ~200 MB are the previous launch's last reads, still in
   // the 256 MiB Infinity Cache (same rows, same per-row work; only the order)
   const bool rev = KM_SMALL_SERP && T.rev;
   auto at = [&](int64_t v) { return rev ? n - 1 - v : v; };
-  float4 nx[DP / 4], nx2[DP / 4];
-  if (PF && row < n) {
+  float4 nx[DP / 4];
+  if (row < n) {
 #pragma unroll
     for (int f = 0; f < DP; f += 4) nx[f / 4] = *reinterpret_cast<const float4*>(X + at(row) * DP + f);
-  }
-  if (PF2 && row + rstride < n) {
-#pragma unroll
-    for (int f = 0; f < DP; f += 4) nx2[f / 4] = *reinterpret_cast<const float4*>(X + at(row + rstride) * DP + f);
   }
   auto row_body = [&](const float (&x)[DP], int64_t row) {
     float k1 = FLT_MAX, k2 = FLT_MAX, k3 = FLT_MAX;
@@ -528,30 +511,11 @@ void k_assign_small(const float* __restrict__ X, int64_t n, int d, int k, const 
 #pragma unroll
     for (int f = 0; f < DP; f += 4) v[f / 4] = *reinterpret_cast<const float4*>(X + r * DP + f);
   };
-  if constexpr (PF2) {
-    for (; row < n; row += 2 * rstride) {
-      float x[DP];
-      unpack(nx, x);
-      if (row + 2 * rstride < n) load_row(nx, at(row + 2 * rstride));
-      row_body(x, at(row));
-      if (row + rstride >= n) break;
-      unpack(nx2, x);
-      if (row + 3 * rstride < n) load_row(nx2, at(row + 3 * rstride));
-      row_body(x, at(row + rstride));
-    }
-  } else {
-    for (; row < n; row += rstride) {
-      float x[DP];
-      if constexpr (PF) {
-        unpack(nx, x);
-        if (row + rstride < n) load_row(nx, at(row + rstride));
-      } else {
-        float4 v[DP / 4];
-        load_row(v, at(row));
-        unpack(v, x);
-      }
-      row_body(x, at(row));
-    }
+  for (; row < n; row += rstride) {
+    float x[DP];
+    unpack(nx, x);
+    if (row + rstride < n) load_row(nx, at(row + rstride));
+    row_body(x, at(row));
   }
   // A queued row, resolved by one wave, lanes over centroids: the
   // reference's float64 norms (kmeans_spark.py:153) in NumPy's pairwise
@@ -759,32 +723,18 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 // lo = RN_f16(xs - hi) for a pair, hi = RN_f16(xs) (the fp16x3 row split).
 // Written in C: the compiler turns it into v_fma_mix forms with the scale
-// folded in and pads the VALU -> MFMA operand hazard itself.  The
-// inline-asm form (KM_SPLIT_ASM=1, one v_fma_mix per element, rounds 1-3)
-// is not safe: hipcc placed an asm v_fma_mixhi_f16 one wait state before the
-// MFMA that reads its register as the B operand -- compiler-emitted VALU
-// writes get two -- and k_fused16 then read stale row halves (567 of 20,000
-// labels wrong in the far-from-origin test, 0 with this form; DESIGN.md
-// section 4).  k_fused's asm happened to be scheduled two or more apart.
-#ifndef KM_SPLIT_ASM
-#define KM_SPLIT_ASM 0
-#endif
+// folded in and pads the VALU -> MFMA operand hazard itself.  An inline-asm
+// form (one v_fma_mix per element, rounds 1-3) was not safe: hipcc placed an
+// asm v_fma_mixhi_f16 one wait state before the MFMA that reads its register
+// as the B operand -- compiler-emitted VALU writes get two -- and k_fused16
+// then read stale row halves (567 of 20,000 labels wrong in the
+// far-from-origin test, 0 with this form).
 __device__ __forceinline__ f16x2 split_lo(f16x2 hp, float xs0, float xs1) {
-#if !KM_SPLIT_ASM
   // xs - hi is exact in fp32; the compiler emits its own v_fma_mix form
   // (with the scale folded in) and sees the writes it must pad
   const f16x2 lo = {(_Float16)(xs0 - (float)hp[0]), (_Float16)(xs1 - (float)hp[1])};
   return lo;
-#else
-  uint32_t lp;
-  asm("v_fma_mixlo_f16 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(lp) : "v"(__builtin_bit_cast(uint32_t, hp)), "v"(xs0));
-  asm("v_fma_mixhi_f16 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-      : "+v"(lp)
-      : "v"(__builtin_bit_cast(uint32_t, hp)), "v"(xs1));
-  return __builtin_bit_cast(f16x2, lp);
-#endif
 }
-
 
 // power-of-two scale: max(|x|, |c|) * s < 2^14 (so |-2cs| < 2^15 < 65504);
 // 1 for non-finite or all-zero data (the keys then force the exact path)
@@ -2141,37 +2091,49 @@ static bool launch_mfma16_ns(int waves, int blocks, size_t lds, hipStream_t s, c
   }
 }
 
+// The 32x32x16 screen.  In the product library every dp that is a multiple of
+// 32 up to 128 has taken k_assign_mfma16 above, so its k_assign_mfma
+// instances exist in the diagnostic build (KM_MFMA16 read from the
+// environment) and in the KM_MFMA16=0 A/B arm only.  false: no instance
 template <int NS>
-static void launch_mfma_ns(int waves, int blocks, size_t lds, hipStream_t s, const MfmaArgs& a) {
-  if (launch_mfma16_ns<NS>(waves, blocks, lds, s, a)) return;
-  if constexpr (NS <= 4) {
-    if (mfma_top2(NS)) {
+static bool launch_mfma_ns(int waves, int blocks, size_t lds, hipStream_t s, const MfmaArgs& a) {
+  if (launch_mfma16_ns<NS>(waves, blocks, lds, s, a)) return true;
+#if defined(KM_DIAG) || !KM_MFMA16
+  constexpr bool built = true;
+#else
+  constexpr bool built = NS % 2 != 0 || NS > 8;
+#endif
+  if constexpr (built) {
+    if constexpr (NS <= 4) {
+      if (mfma_top2(NS)) {
+        if (waves == 4)
+          hipLaunchKernelGGL((k_assign_mfma<NS, 4, true>), dim3(blocks), dim3(256), lds, s, a);
+        else if (waves == 16)
+          hipLaunchKernelGGL((k_assign_mfma<NS, 16, true>), dim3(blocks), dim3(1024), lds, s, a);
+        else if (waves == 12)
+          hipLaunchKernelGGL((k_assign_mfma<NS, 12, true>), dim3(blocks), dim3(768), lds, s, a);
+        else
+          hipLaunchKernelGGL((k_assign_mfma<NS, 8, true>), dim3(blocks), dim3(512), lds, s, a);
+        return true;
+      }
+    }
+    if constexpr (NS >= 12) {
+      hipLaunchKernelGGL((k_assign_mfma<NS, 4>), dim3(blocks), dim3(256), lds, s, a);
+    } else {
       if (waves == 4)
-        hipLaunchKernelGGL((k_assign_mfma<NS, 4, true>), dim3(blocks), dim3(256), lds, s, a);
-      else if (waves == 16)
-        hipLaunchKernelGGL((k_assign_mfma<NS, 16, true>), dim3(blocks), dim3(1024), lds, s, a);
-      else if (waves == 12)
-        hipLaunchKernelGGL((k_assign_mfma<NS, 12, true>), dim3(blocks), dim3(768), lds, s, a);
+        hipLaunchKernelGGL((k_assign_mfma<NS, 4>), dim3(blocks), dim3(256), lds, s, a);
+      else if (waves == 16) {
+        if constexpr (NS <= 4)
+          hipLaunchKernelGGL((k_assign_mfma<NS, 16>), dim3(blocks), dim3(1024), lds, s, a);
+        else  // no 16-wave instance past dp 64 (spills): the 8-wave one, never a silent no-launch
+          hipLaunchKernelGGL((k_assign_mfma<NS, 8>), dim3(blocks), dim3(512), lds, s, a);
+      } else if (waves == 12)
+        hipLaunchKernelGGL((k_assign_mfma<NS, 12>), dim3(blocks), dim3(768), lds, s, a);
       else
-        hipLaunchKernelGGL((k_assign_mfma<NS, 8, true>), dim3(blocks), dim3(512), lds, s, a);
-      return;
+        hipLaunchKernelGGL((k_assign_mfma<NS, 8>), dim3(blocks), dim3(512), lds, s, a);
     }
   }
-  if constexpr (NS >= 12) {
-    hipLaunchKernelGGL((k_assign_mfma<NS, 4>), dim3(blocks), dim3(256), lds, s, a);
-  } else {
-    if (waves == 4)
-      hipLaunchKernelGGL((k_assign_mfma<NS, 4>), dim3(blocks), dim3(256), lds, s, a);
-    else if (waves == 16) {
-      if constexpr (NS <= 4)
-        hipLaunchKernelGGL((k_assign_mfma<NS, 16>), dim3(blocks), dim3(1024), lds, s, a);
-      else  // no 16-wave instance past dp 64 (spills): the 8-wave one, never a silent no-launch
-        hipLaunchKernelGGL((k_assign_mfma<NS, 8>), dim3(blocks), dim3(512), lds, s, a);
-    } else if (waves == 12)
-      hipLaunchKernelGGL((k_assign_mfma<NS, 12>), dim3(blocks), dim3(768), lds, s, a);
-    else
-      hipLaunchKernelGGL((k_assign_mfma<NS, 8>), dim3(blocks), dim3(512), lds, s, a);
-  }
+  return built;
 }
 
 hipError_t launch_assign_mfma(const float* X, const Geometry& g, const _Float16* Chi, const _Float16* Clo,
@@ -2220,18 +2182,19 @@ hipError_t launch_assign_mfma(const float* X, const Geometry& g, const _Float16*
   MfmaArgs a{X, g.n, g.k, g.kp, KC, seg, Chi, Clo, cn2s, cmax, xabs, cabs, labels, queue, qcount, gate,
              use_cand ? cand : nullptr, cand_ctr, cand_cap, (one && g.dp % 32 == 0 && g.dp <= 256) ? 1 : 0, C32,
              chg, chg_cnt};
+  bool launched = false;
   switch (g.dp / 16) {
-    case 1: launch_mfma_ns<1>(waves, nb, lds, s, a); break;
-    case 2: launch_mfma_ns<2>(waves, nb, lds, s, a); break;
-    case 3: launch_mfma_ns<3>(waves, nb, lds, s, a); break;
-    case 4: launch_mfma_ns<4>(waves, nb, lds, s, a); break;
-    case 6: launch_mfma_ns<6>(waves, nb, lds, s, a); break;
-    case 8: launch_mfma_ns<8>(waves, nb, lds, s, a); break;
-    case 12: launch_mfma_ns<12>(waves, nb, lds, s, a); break;
-    case 16: launch_mfma_ns<16>(waves, nb, lds, s, a); break;
+    case 1: launched = launch_mfma_ns<1>(waves, nb, lds, s, a); break;
+    case 2: launched = launch_mfma_ns<2>(waves, nb, lds, s, a); break;
+    case 3: launched = launch_mfma_ns<3>(waves, nb, lds, s, a); break;
+    case 4: launched = launch_mfma_ns<4>(waves, nb, lds, s, a); break;
+    case 6: launched = launch_mfma_ns<6>(waves, nb, lds, s, a); break;
+    case 8: launched = launch_mfma_ns<8>(waves, nb, lds, s, a); break;
+    case 12: launched = launch_mfma_ns<12>(waves, nb, lds, s, a); break;
+    case 16: launched = launch_mfma_ns<16>(waves, nb, lds, s, a); break;
     default: return hipErrorInvalidValue;
   }
-  return hipGetLastError();
+  return launched ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // abs max of the data (fp16 scaling of the MFMA screen), accumulated over loads
@@ -3249,17 +3212,9 @@ hipError_t launch_fused(const float* X, const float* xnorm, const Geometry& g, c
       KM_TIMED_LAUNCH((k_fused16<NS2_, NB_, true, false>), dim3(nbk), dim3(256), lds, s, a);         \
     else if (with_stats)                                                                                \
       KM_TIMED_LAUNCH((k_fused16<NS2_, NB_, true>), dim3(nbk), dim3(256), lds, s, a);                \
-    else if (KM_F16_PREDICT == 1)                                                                       \
-      KM_TIMED_LAUNCH((k_fused16<NS2_, NB_, true>), dim3(nbk), dim3(256), lds_s, s, a);              \
-    else if (KM_F16_PREDICT == 2)                                                                       \
-      KM_TIMED_LAUNCH((k_fused16<NS2_, NB_, false, false>), dim3(nbk), dim3(256), lds, s, a);        \
     else                                                                                                \
       KM_TIMED_LAUNCH((k_fused16<NS2_, NB_, false>), dim3(nbk), dim3(256), lds, s, a);               \
     break;
-#ifndef KM_F16_PREDICT
-#define KM_F16_PREDICT 0
-#endif
-  const size_t lds_s = (size_t)g.kp * 4 + (size_t)(g.dp + 1) * g.kp * 8;
   if (shape16) {
     switch ((g.dp / 32) * 100 + nb) {
       KM_FUSED16_CASE(2, 2) KM_FUSED16_CASE(2, 4) KM_FUSED16_CASE(2, 6) KM_FUSED16_CASE(2, 8)
@@ -3273,11 +3228,16 @@ hipError_t launch_fused(const float* X, const float* xnorm, const Geometry& g, c
   }
 #undef KM_FUSED16_CASE
   switch (ns * 100 + nb) {
+    // dp a multiple of 32 runs on k_fused16 in the product library: its 32x32x16
+    // instances exist in the diagnostic build (KM_FUSED16 read from the
+    // environment) and in the KM_FUSED16=0 A/B arm only
+#if defined(KM_DIAG) || !KM_FUSED16
     KM_FUSED_CASE(4, 2) KM_FUSED_CASE(4, 4) KM_FUSED_CASE(4, 6) KM_FUSED_CASE(4, 8)
     KM_FUSED_CASE(2, 2) KM_FUSED_CASE(2, 4) KM_FUSED_CASE(2, 6) KM_FUSED_CASE(2, 8) KM_FUSED_CASE(2, 12)
     KM_FUSED_CASE(2, 16)
-    KM_FUSED_CASE(3, 2) KM_FUSED_CASE(3, 4) KM_FUSED_CASE(3, 6) KM_FUSED_CASE(3, 8)
     KM_FUSED_CASE(8, 2) KM_FUSED_CASE(8, 4)
+#endif
+    KM_FUSED_CASE(3, 2) KM_FUSED_CASE(3, 4) KM_FUSED_CASE(3, 6) KM_FUSED_CASE(3, 8)
     default:
       return hipErrorInvalidValue;
   }
@@ -4066,26 +4026,53 @@ hipError_t launch_resolve(const float* X, const Geometry& g, const double* C64, 
 // chunks of 64 contiguous rows as coalesced float4 loads (8 in flight per
 // lane), labels broadcast from one coalesced load; one float64 global atomic
 // per non-zero table entry at the end.
-// ---------------------------------------------------------------------------
-static constexpr int STATS_LDS = 156 * 1024;
-
 // The workgroup also owns a feature range [f0, f0 + fr) (blockIdx.z):
 // splitting the features instead of the clusters keeps X read once when
 // k (d+1) doubles exceed LDS but k (fr+1) fit (c4: 1024 clusters x 16 features).
-template <bool SSE = false>
+// An LDS table row is fr + 1 slots: features, then the row count n, which
+// reaches the global statistics from feature range 0 only.
+// SSE (compute_sse, kmeans_spark.py:224-237) in the same pass: each
+// (row, feature range) is summed by exactly one workgroup (the one owning
+// the row's cluster).  Per row it adds the float64 residual to the fp32
+// image c' of the pre-update centroid (C32, 16 B per 4 features gathered
+// from L2 instead of C64's 32 B); at the flush it corrects to the float64
+// centroid c = c' + delta per cluster and feature, exactly in algebra:
+//   sum_rows (x - c)^2 = sum_rows (x - c')^2 - 2 delta (S - n c') + n delta^2
+// with S, n this workgroup's own partial sums and count (linear, so the
+// workgroups' corrections add up).  |delta| <= 2^-24 |c|, so the
+// correction's own rounding is ~2^-75 n |c|^2
+//
+// W, weighted (fit(..., sample_weight=w)): a float64 weight per row.  Per
+// cluster S = sum w x into the sum slots, the row count n into the count slot
+// (clusters are empty by rows, not by weight) and W = sum w into wsum[k] (the
+// k doubles behind the SSE slot: the update's divisor).  The weights of a
+// chunk of 64 rows come from one coalesced 8-byte load per lane and reach the
+// rows' lane groups by shuffle, like the labels.  The table row is fr + 2
+// slots: features, W, n; W and n reach the global statistics from feature
+// range 0 only.  SSE: sum w (x - c)^2, by the same identity with weighted sums:
+//   sum w (x - c)^2 = sum w (x - c')^2 - 2 delta (S - W c') + W delta^2
+// (every feature range keeps W in its table for the correction).  The float64
+// centroids have row stride c64s (the small path keeps [k][d], no padded
+// image); the unweighted instance reads them at stride dp.
+// ---------------------------------------------------------------------------
+static constexpr int STATS_LDS = 156 * 1024;
+
+template <bool SSE, bool W>
 __global__ __launch_bounds__(1024) void k_stats(const float* __restrict__ X, int64_t n, int d, int dp, int k,
                                                 const int32_t* __restrict__ labels, double* __restrict__ stats,
-                                                int kr, int fr, int64_t rows_per_block, const double* __restrict__ C64P,
+                                                int kr, int fr, int64_t rows_per_block, const double* __restrict__ C64,
                                                 const float* __restrict__ C32, double* __restrict__ sse,
-                                                const int* __restrict__ gate) {
+                                                const int* __restrict__ gate, const double* __restrict__ w,
+                                                double* __restrict__ wsum, int c64s) {
   if (*gate) return;  // a stopped batch (km_update_async): the rest of it is a no-op
   if constexpr (!SSE) sse = nullptr;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   double* tab = reinterpret_cast<double*>(smem);
-  // LDS row of a cluster: fr feature slots + count.  Feature f0 + 4m + c is
-  // stored at slot c*L + m (L = fr/4 lanes per row), so the 4 atomics of a
-  // float4 each hit L consecutive doubles: no bank conflicts.
-  const int RS = fr + 1;
+  // LDS row of a cluster: fr feature slots + count (weighted: W at slot fr, n
+  // at fr + 1).  Feature f0 + 4m + c is stored at slot c*L + m (L = fr/4 lanes
+  // per row), so the 4 atomics of a float4 each hit L consecutive doubles: no
+  // bank conflicts.
+  const int RS = fr + (W ? 2 : 1);
   const int L = fr / 4;
   const int c0 = blockIdx.y * kr;
   const int c1 = min(k, c0 + kr);
@@ -4106,21 +4093,21 @@ __global__ __launch_bounds__(1024) void k_stats(const float* __restrict__ X, int
   // whole row idle (lane q = P would repeat row u + 1's first features)
   const bool act = q < P;
   constexpr int U = SSE ? 6 : 8;  // float4 rows in flight per lane (SSE: and as many centroid images)
-  // SSE (compute_sse, kmeans_spark.py:224-237) in the same pass: each
-  // (row, feature range) is summed by exactly one workgroup (the one owning
-  // the row's cluster).  Per row it adds the float64 residual to the fp32
-  // image c' of the pre-update centroid (C32, 16 B per 4 features gathered
-  // from L2 instead of C64P's 32 B); at the flush it corrects to the float64
-  // centroid c = c' + delta per cluster and feature, exactly in algebra:
-  //   sum_rows (x - c)^2 = sum_rows (x - c')^2 - 2 delta (S - n c') + n delta^2
-  // with S, n this workgroup's own partial sums and count (linear, so the
-  // workgroups' corrections add up).  |delta| <= 2^-24 |c|, so the
-  // correction's own rounding is ~2^-75 n |c|^2
   double ss = 0.0;
   for (int64_t cr = r0 + (int64_t)wave * 64; cr < r1; cr += (int64_t)nwaves * 64) {
     const int nrow = (int)min((int64_t)64, r1 - cr);
     const int labreg = lane < nrow ? labels[cr + lane] : -1;
-    if ((counts || sse) && lane < nrow && labreg >= c0 && labreg < c1) atomicAdd(tab + (labreg - c0) * RS + fr, 1.0);
+    double wreg = 0.0;
+    if constexpr (W) {
+      wreg = lane < nrow ? w[cr + lane] : 0.0;
+      if (lane < nrow && labreg >= c0 && labreg < c1) {
+        double* t = tab + (labreg - c0) * RS + fr;
+        if (counts || sse) atomicAdd(t, wreg);
+        if (counts) atomicAdd(t + 1, 1.0);
+      }
+    } else {
+      if ((counts || sse) && lane < nrow && labreg >= c0 && labreg < c1) atomicAdd(tab + (labreg - c0) * RS + fr, 1.0);
+    }
     const float* base = X + cr * dp + f0;
     for (int rb = 0; rb < nrow; rb += P * U) {
       float4 v[U];
@@ -4133,8 +4120,12 @@ __global__ __launch_bounds__(1024) void k_stats(const float* __restrict__ X, int
       // the rows' labels, then (SSE) every row's centroid image gathered
       // before any is used: U L2 loads in flight instead of U dependent ones
       int labs[U];
+      [[maybe_unused]] double wv[U];
 #pragma unroll
-      for (int u = 0; u < U; ++u) labs[u] = __shfl(labreg, (rb + u * P + q) & 63);
+      for (int u = 0; u < U; ++u) {
+        labs[u] = __shfl(labreg, (rb + u * P + q) & 63);
+        if constexpr (W) wv[u] = __shfl(wreg, (rb + u * P + q) & 63);
+      }
       float4 cg[U];
       if (sse) {
 #pragma unroll
@@ -4151,18 +4142,34 @@ __global__ __launch_bounds__(1024) void k_stats(const float* __restrict__ X, int
         const int lab = labs[u];
         if (act && rr < nrow && lab >= c0 && lab < c1) {
           double* t = tab + (lab - c0) * RS + mm;
-          atomicAdd(t, (double)v[u].x);
-          atomicAdd(t + L, (double)v[u].y);
-          atomicAdd(t + 2 * L, (double)v[u].z);
-          atomicAdd(t + 3 * L, (double)v[u].w);
+          if constexpr (W) {
+            const double wr = wv[u];
+            atomicAdd(t, wr * (double)v[u].x);
+            atomicAdd(t + L, wr * (double)v[u].y);
+            atomicAdd(t + 2 * L, wr * (double)v[u].z);
+            atomicAdd(t + 3 * L, wr * (double)v[u].w);
+          } else {
+            atomicAdd(t, (double)v[u].x);
+            atomicAdd(t + L, (double)v[u].y);
+            atomicAdd(t + 2 * L, (double)v[u].z);
+            atomicAdd(t + 3 * L, (double)v[u].w);
+          }
           if (sse) {  // padded features are 0 - 0
             const float4 c = cg[u];
             const double t0 = (double)v[u].x - (double)c.x, t1 = (double)v[u].y - (double)c.y;
             const double t2 = (double)v[u].z - (double)c.z, t3 = (double)v[u].w - (double)c.w;
-            ss = fma(t0, t0, ss);
-            ss = fma(t1, t1, ss);
-            ss = fma(t2, t2, ss);
-            ss = fma(t3, t3, ss);
+            if constexpr (W) {
+              const double wr = wv[u];
+              ss = fma(wr * t0, t0, ss);
+              ss = fma(wr * t1, t1, ss);
+              ss = fma(wr * t2, t2, ss);
+              ss = fma(wr * t3, t3, ss);
+            } else {
+              ss = fma(t0, t0, ss);
+              ss = fma(t1, t1, ss);
+              ss = fma(t2, t2, ss);
+              ss = fma(t3, t3, ss);
+            }
           }
         }
       }
@@ -4175,7 +4182,27 @@ __global__ __launch_bounds__(1024) void k_stats(const float* __restrict__ X, int
     const int p = i - j * RS;
     const double v = tab[i];
     int f;
-    if (p == fr) {
+    if constexpr (W) {
+      if (p >= fr) {
+        if (!counts || v == 0.0) continue;  // W and n only from feature range 0
+        if (p == fr)
+          atomicAdd(wsum + c0 + j, v);
+        else
+          atomicAdd(stats + (size_t)(c0 + j) * d1 + d, v);
+        continue;
+      }
+      f = f0 + 4 * (p % L) + p / L;
+      if (f >= d) continue;  // zero padding
+      if (sse) {
+        // delta (S - W c') and W delta^2 of this (cluster, feature)
+        const double Wc = tab[j * RS + fr];
+        if (Wc != 0.0) {
+          const double cp = (double)C32[(size_t)(c0 + j) * dp + f];
+          const double dl = C64[(size_t)(c0 + j) * c64s + f] - cp;
+          ss += dl * (Wc * dl - 2.0 * (v - Wc * cp));
+        }
+      }
+    } else if (p == fr) {
       if (!counts) continue;  // counts only from feature range 0
       f = d;
     } else {
@@ -4187,7 +4214,7 @@ __global__ __launch_bounds__(1024) void k_stats(const float* __restrict__ X, int
         const double n = tab[j * RS + fr];
         if (n != 0.0) {
           const double cp = (double)C32[(size_t)(c0 + j) * dp + f];
-          const double dl = C64P[(size_t)(c0 + j) * dp + f] - cp;
+          const double dl = C64[(size_t)(c0 + j) * dp + f] - cp;
           ss += dl * (n * dl - 2.0 * (v - n * cp));
         }
       }
@@ -4239,185 +4266,20 @@ void stats_ranges(const Geometry& g, int* fr_out, int* kr_out, int extra) {
   *kr_out = best_kr;
 }
 
-hipError_t launch_stats(const float* X, const Geometry& g, const int32_t* labels, double* stats, int n_cu,
-                        const int* gate, hipStream_t s, const double* C64P, const float* C32) {
+// w != nullptr: the weighted instance; C64 then has row stride c64s
+hipError_t launch_stats(const float* X, const Geometry& g, const int32_t* labels, const double* w, double* stats,
+                        int n_cu, const int* gate, hipStream_t s, const double* C64, int c64s, const float* C32) {
   if (g.n == 0) return hipSuccess;
-  if (C64P && !C32) return hipErrorInvalidValue;
+  if (C64 && !C32) return hipErrorInvalidValue;
+  if (!w && C64 && c64s != g.dp) return hipErrorInvalidValue;  // the unweighted instance reads C64 at stride dp
   if (g.dp > WIDE_MAX_DP || g.dp % 4) return hipErrorInvalidValue;
+  const int extra = w ? 2 : 1;
   int fr = 0, kr = 0;
-  stats_ranges(g, &fr, &kr);
+  stats_ranges(g, &fr, &kr, extra);
   if (kr < 1) return hipErrorInvalidValue;
   const int ranges = (g.k + kr - 1) / kr;
   const int franges = g.dp / fr;
-  const size_t lds = (size_t)kr * (fr + 1) * 8;
-  int per_cu = (int)((160 * 1024) / (lds + 1024));
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 2) per_cu = 2;
-  int64_t bx = (int64_t)n_cu * per_cu / (ranges * franges);
-  if (bx < 1) bx = 1;
-  const int64_t min_rows = 4096;
-  if (bx > (g.n + min_rows - 1) / min_rows) bx = (g.n + min_rows - 1) / min_rows;
-  int64_t rpb = (g.n + bx - 1) / bx;
-  rpb = (rpb + 63) / 64 * 64;
-  if (C64P)
-    hipLaunchKernelGGL((k_stats<true>), dim3((unsigned)bx, (unsigned)ranges, (unsigned)franges), dim3(1024), lds,
-                       s, X, g.n, g.d, g.dp, g.k, labels, stats, kr, fr, rpb, C64P, C32,
-                       stats + (size_t)g.k * (g.d + 1), gate);
-  else
-    hipLaunchKernelGGL((k_stats<false>), dim3((unsigned)bx, (unsigned)ranges, (unsigned)franges), dim3(1024),
-                       lds, s, X, g.n, g.d, g.dp, g.k, labels, stats, kr, fr, rpb, C64P, C32, (double*)nullptr, gate);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// Weighted partial statistics (fit(..., sample_weight=w)): the k_stats scheme
-// with a float64 weight per row.  Per cluster S = sum w x into the sum slots,
-// the row count n into the count slot (clusters are empty by rows, not by
-// weight) and W = sum w into wsum[k] (the k doubles behind the SSE slot: the
-// update's divisor).  The weights of a chunk of 64 rows come from one
-// coalesced 8-byte load per lane and reach the rows' lane groups by shuffle,
-// like the labels.  An LDS table row is fr + 2 slots: features, W, n; W and n
-// reach the global statistics from feature range 0 only.
-// SSE: sum w (x - c)^2, by the same fp32-image identity with weighted sums:
-//   sum w (x - c)^2 = sum w (x - c')^2 - 2 delta (S - W c') + W delta^2
-// (every feature range keeps W in its table for the correction).
-// ---------------------------------------------------------------------------
-template <bool SSE = false>
-__global__ __launch_bounds__(1024) void k_wstats(const float* __restrict__ X, int64_t n, int d, int dp, int k,
-                                                 const int32_t* __restrict__ labels, const double* __restrict__ w,
-                                                 double* __restrict__ stats, double* __restrict__ wsum, int kr,
-                                                 int fr, int64_t rows_per_block, const double* __restrict__ C64,
-                                                 int c64s, const float* __restrict__ C32, double* __restrict__ sse,
-                                                 const int* __restrict__ gate) {
-  if (*gate) return;  // a stopped batch (km_update_async): the rest of it is a no-op
-  if constexpr (!SSE) sse = nullptr;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  double* tab = reinterpret_cast<double*>(smem);
-  // feature f0 + 4m + c at slot c*L + m (as k_stats), W at slot fr, n at fr + 1
-  const int RS = fr + 2;
-  const int L = fr / 4;
-  const int c0 = blockIdx.y * kr;
-  const int c1 = min(k, c0 + kr);
-  const int f0 = blockIdx.z * fr;
-  const bool counts = blockIdx.z == 0;
-  const int nent = (c1 - c0) * RS;
-  for (int i = threadIdx.x; i < nent; i += blockDim.x) tab[i] = 0.0;
-  __syncthreads();
-  const int64_t r0 = (int64_t)blockIdx.x * rows_per_block;
-  const int64_t r1 = min(n, r0 + rows_per_block);
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int nwaves = blockDim.x >> 6;
-  const int P = 64 / L;
-  const int q = lane / L;
-  const int mm = lane % L;
-  const bool act = q < P;
-  constexpr int U = SSE ? 6 : 8;
-  double ss = 0.0;
-  for (int64_t cr = r0 + (int64_t)wave * 64; cr < r1; cr += (int64_t)nwaves * 64) {
-    const int nrow = (int)min((int64_t)64, r1 - cr);
-    const int labreg = lane < nrow ? labels[cr + lane] : -1;
-    const double wreg = lane < nrow ? w[cr + lane] : 0.0;
-    if (lane < nrow && labreg >= c0 && labreg < c1) {
-      double* t = tab + (labreg - c0) * RS + fr;
-      if (counts || sse) atomicAdd(t, wreg);
-      if (counts) atomicAdd(t + 1, 1.0);
-    }
-    const float* base = X + cr * dp + f0;
-    for (int rb = 0; rb < nrow; rb += P * U) {
-      float4 v[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int rr = rb + u * P + q;
-        v[u] = (act && rr < nrow) ? *reinterpret_cast<const float4*>(base + (size_t)rr * dp + 4 * mm)
-                                  : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-      int labs[U];
-      double wv[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        labs[u] = __shfl(labreg, (rb + u * P + q) & 63);
-        wv[u] = __shfl(wreg, (rb + u * P + q) & 63);
-      }
-      float4 cg[U];
-      if (sse) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int rr = rb + u * P + q;
-          const bool mine = act && rr < nrow && labs[u] >= c0 && labs[u] < c1;
-          cg[u] = mine ? *reinterpret_cast<const float4*>(C32 + (size_t)labs[u] * dp + f0 + 4 * mm)
-                       : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int rr = rb + u * P + q;
-        const int lab = labs[u];
-        if (act && rr < nrow && lab >= c0 && lab < c1) {
-          const double wr = wv[u];
-          double* t = tab + (lab - c0) * RS + mm;
-          atomicAdd(t, wr * (double)v[u].x);
-          atomicAdd(t + L, wr * (double)v[u].y);
-          atomicAdd(t + 2 * L, wr * (double)v[u].z);
-          atomicAdd(t + 3 * L, wr * (double)v[u].w);
-          if (sse) {  // padded features are 0 - 0
-            const float4 c = cg[u];
-            const double t0 = (double)v[u].x - (double)c.x, t1 = (double)v[u].y - (double)c.y;
-            const double t2 = (double)v[u].z - (double)c.z, t3 = (double)v[u].w - (double)c.w;
-            ss = fma(wr * t0, t0, ss);
-            ss = fma(wr * t1, t1, ss);
-            ss = fma(wr * t2, t2, ss);
-            ss = fma(wr * t3, t3, ss);
-          }
-        }
-      }
-    }
-  }
-  __syncthreads();
-  const int d1 = d + 1;
-  for (int i = threadIdx.x; i < nent; i += blockDim.x) {
-    const int j = i / RS;
-    const int p = i - j * RS;
-    const double v = tab[i];
-    if (p >= fr) {
-      if (!counts || v == 0.0) continue;  // W and n only from feature range 0
-      if (p == fr)
-        atomicAdd(wsum + c0 + j, v);
-      else
-        atomicAdd(stats + (size_t)(c0 + j) * d1 + d, v);
-      continue;
-    }
-    const int f = f0 + 4 * (p % L) + p / L;
-    if (f >= d) continue;  // zero padding
-    if (sse) {
-      // delta (S - W c') and W delta^2 of this (cluster, feature)
-      const double W = tab[j * RS + fr];
-      if (W != 0.0) {
-        const double cp = (double)C32[(size_t)(c0 + j) * dp + f];
-        const double dl = C64[(size_t)(c0 + j) * c64s + f] - cp;
-        ss += dl * (W * dl - 2.0 * (v - W * cp));
-      }
-    }
-    if (v == 0.0) continue;
-    atomicAdd(stats + (size_t)(c0 + j) * d1 + f, v);
-  }
-  if (sse) {
-    ss = wave_sum(ss);
-    if (lane == 0 && ss != 0.0) atomicAdd(sse, ss);
-  }
-}
-
-hipError_t launch_wstats(const float* X, const Geometry& g, const int32_t* labels, const double* w, double* stats,
-                         int n_cu, const int* gate, hipStream_t s, const double* C64, int c64s, const float* C32) {
-  if (g.n == 0) return hipSuccess;
-  if (!w || (C64 && !C32)) return hipErrorInvalidValue;
-  if (g.dp > WIDE_MAX_DP || g.dp % 4) return hipErrorInvalidValue;
-  int fr = 0, kr = 0;
-  stats_ranges(g, &fr, &kr, 2);
-  if (kr < 1) return hipErrorInvalidValue;
-  const int ranges = (g.k + kr - 1) / kr;
-  const int franges = g.dp / fr;
-  const size_t lds = (size_t)kr * (fr + 2) * 8;
+  const size_t lds = (size_t)kr * (fr + extra) * 8;
   int per_cu = (int)((160 * 1024) / (lds + 1024));
   if (per_cu < 1) per_cu = 1;
   if (per_cu > 2) per_cu = 2;
@@ -4429,12 +4291,22 @@ hipError_t launch_wstats(const float* X, const Geometry& g, const int32_t* label
   rpb = (rpb + 63) / 64 * 64;
   double* sse = stats + (size_t)g.k * (g.d + 1);
   double* wsum = sse + 1;
-  if (C64)
-    hipLaunchKernelGGL((k_wstats<true>), dim3((unsigned)bx, (unsigned)ranges, (unsigned)franges), dim3(1024), lds, s, X,
-                       g.n, g.d, g.dp, g.k, labels, w, stats, wsum, kr, fr, rpb, C64, c64s, C32, sse, gate);
-  else
-    hipLaunchKernelGGL((k_wstats<false>), dim3((unsigned)bx, (unsigned)ranges, (unsigned)franges), dim3(1024), lds, s, X,
-                       g.n, g.d, g.dp, g.k, labels, w, stats, wsum, kr, fr, rpb, C64, c64s, C32, (double*)nullptr, gate);
+  const dim3 grid((unsigned)bx, (unsigned)ranges, (unsigned)franges);
+#define KM_STATS(SSE_, W_)                                                                                    \
+  hipLaunchKernelGGL((k_stats<SSE_, W_>), grid, dim3(1024), lds, s, X, g.n, g.d, g.dp, g.k, labels, stats, kr, \
+                     fr, rpb, C64, C32, SSE_ ? sse : (double*)nullptr, gate, w, wsum, c64s)
+  if (w) {
+    if (C64)
+      KM_STATS(true, true);
+    else
+      KM_STATS(false, true);
+  } else {
+    if (C64)
+      KM_STATS(true, false);
+    else
+      KM_STATS(false, false);
+  }
+#undef KM_STATS
   return hipGetLastError();
 }
 
@@ -4602,11 +4474,16 @@ __global__ __launch_bounds__(SCAT_THREADS) void k_scatter(const int32_t* __restr
 // With C64P the SSE residuals ride along: the sorted order keeps a lane's
 // centroid features constant over a run, so they are reloaded only when the
 // cluster changes.
-template <int L>  // lanes per row = dp / 4
+// W, weighted (fit(..., sample_weight=w)): the row's float64 weight is
+// gathered beside the row (w[perm[pos]], 8 bytes per row through the same
+// index).  The lane group accumulates S += w x; its first lane also W += w,
+// flushed to wsum[cluster] with the sums.  The SSE residuals are w (x - c)^2.
+template <int L, bool W>  // lanes per row = dp / 4
 __global__ __launch_bounds__(256) void k_segsum(const float* __restrict__ X, int d, int64_t n,
                                                 const uint32_t* __restrict__ perm, const int32_t* __restrict__ slab,
                                                 double* __restrict__ stats, const double* __restrict__ C64P,
-                                                double* __restrict__ sse, const int* __restrict__ gate) {
+                                                double* __restrict__ sse, const int* __restrict__ gate,
+                                                const double* __restrict__ w, double* __restrict__ wsum) {
   if (*gate) return;  // a stopped batch (km_update_async): the rest of it is a no-op
   constexpr int P = 64 / L;  // rows per wave-instruction
   constexpr int U = 4;       // instructions in flight
@@ -4623,6 +4500,7 @@ __global__ __launch_bounds__(256) void k_segsum(const float* __restrict__ X, int
   const int d1 = d + 1;
   int cur = -1;
   double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  [[maybe_unused]] double aw = 0.0;
   double c0 = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0, ss = 0.0;
   auto flush = [&]() {
     if (cur >= 0) {
@@ -4631,21 +4509,27 @@ __global__ __launch_bounds__(256) void k_segsum(const float* __restrict__ X, int
       if (4 * m + 1 < d) atomicAdd(o + 1, a1);
       if (4 * m + 2 < d) atomicAdd(o + 2, a2);
       if (4 * m + 3 < d) atomicAdd(o + 3, a3);
+      if constexpr (W)
+        if (m == 0) atomicAdd(wsum + cur, aw);
     }
     a0 = a1 = a2 = a3 = 0.0;
+    if constexpr (W) aw = 0.0;
   };
   for (int64_t base = p0; act && base < p1; base += P * U) {
     float4 v[U];
     int lb[U];
+    [[maybe_unused]] double wv[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t pos = base + u * P + q;
       if (pos < p1) {
         const uint32_t row = perm[pos];
         lb[u] = slab[pos];
+        if constexpr (W) wv[u] = w[row];
         v[u] = *reinterpret_cast<const float4*>(X + (size_t)row * DP + 4 * m);
       } else {
         lb[u] = -1;
+        if constexpr (W) wv[u] = 0.0;
         v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
       }
     }
@@ -4664,17 +4548,34 @@ __global__ __launch_bounds__(256) void k_segsum(const float* __restrict__ X, int
           c3 = cb.y;
         }
       }
-      a0 += (double)v[u].x;
-      a1 += (double)v[u].y;
-      a2 += (double)v[u].z;
-      a3 += (double)v[u].w;
+      if constexpr (W) {
+        const double wr = wv[u];
+        a0 = fma(wr, (double)v[u].x, a0);
+        a1 = fma(wr, (double)v[u].y, a1);
+        a2 = fma(wr, (double)v[u].z, a2);
+        a3 = fma(wr, (double)v[u].w, a3);
+        aw += wr;
+      } else {
+        a0 += (double)v[u].x;
+        a1 += (double)v[u].y;
+        a2 += (double)v[u].z;
+        a3 += (double)v[u].w;
+      }
       if (C64P) {  // padded features are 0 - 0
         const double t0 = (double)v[u].x - c0, t1 = (double)v[u].y - c1;
         const double t2 = (double)v[u].z - c2, t3 = (double)v[u].w - c3;
-        ss = fma(t0, t0, ss);
-        ss = fma(t1, t1, ss);
-        ss = fma(t2, t2, ss);
-        ss = fma(t3, t3, ss);
+        if constexpr (W) {
+          const double wr = wv[u];
+          ss = fma(wr * t0, t0, ss);
+          ss = fma(wr * t1, t1, ss);
+          ss = fma(wr * t2, t2, ss);
+          ss = fma(wr * t3, t3, ss);
+        } else {
+          ss = fma(t0, t0, ss);
+          ss = fma(t1, t1, ss);
+          ss = fma(t2, t2, ss);
+          ss = fma(t3, t3, ss);
+        }
       }
     }
   }
@@ -4692,101 +4593,6 @@ __global__ void k_put_counts(const uint32_t* __restrict__ cnt, int k, int d, dou
   if (j < k) stats[(size_t)j * (d + 1) + d] = (double)cnt[j];
 }
 
-// Weighted segmented sums (fit(..., sample_weight=w)): k_segsum with the
-// row's float64 weight gathered beside the row (w[perm[pos]], 8 bytes per
-// row through the same index).  The lane group accumulates S += w x; its
-// first lane also W += w, flushed to wsum[cluster] with the sums.  The SSE
-// residuals w (x - c)^2 to the float64 centroid ride along as in k_segsum.
-template <int L>  // lanes per row = dp / 4
-__global__ __launch_bounds__(256) void k_wsegsum(const float* __restrict__ X, int d, int64_t n,
-                                                 const uint32_t* __restrict__ perm, const int32_t* __restrict__ slab,
-                                                 const double* __restrict__ w, double* __restrict__ stats,
-                                                 double* __restrict__ wsum, const double* __restrict__ C64P,
-                                                 double* __restrict__ sse, const int* __restrict__ gate) {
-  if (*gate) return;  // a stopped batch (km_update_async): the rest of it is a no-op
-  constexpr int P = 64 / L;
-  constexpr int U = 4;
-  constexpr int DP = 4 * L;
-  const int lane = threadIdx.x & 63;
-  const int q = lane / L;
-  const int m = lane % L;
-  const bool act = q < P;
-  const int64_t gw = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  const int64_t per = (n + nw - 1) / nw;
-  const int64_t p0 = gw * per;
-  const int64_t p1 = p0 + per < n ? p0 + per : n;
-  const int d1 = d + 1;
-  int cur = -1;
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, aw = 0.0;
-  double c0 = 0.0, c1 = 0.0, c2 = 0.0, c3 = 0.0, ss = 0.0;
-  auto flush = [&]() {
-    if (cur >= 0) {
-      double* o = stats + (size_t)cur * d1 + 4 * m;
-      if (4 * m + 0 < d) atomicAdd(o + 0, a0);
-      if (4 * m + 1 < d) atomicAdd(o + 1, a1);
-      if (4 * m + 2 < d) atomicAdd(o + 2, a2);
-      if (4 * m + 3 < d) atomicAdd(o + 3, a3);
-      if (m == 0) atomicAdd(wsum + cur, aw);
-    }
-    a0 = a1 = a2 = a3 = aw = 0.0;
-  };
-  for (int64_t base = p0; act && base < p1; base += P * U) {
-    float4 v[U];
-    int lb[U];
-    double wv[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t pos = base + u * P + q;
-      if (pos < p1) {
-        const uint32_t row = perm[pos];
-        lb[u] = slab[pos];
-        wv[u] = w[row];
-        v[u] = *reinterpret_cast<const float4*>(X + (size_t)row * DP + 4 * m);
-      } else {
-        lb[u] = -1;
-        wv[u] = 0.0;
-        v[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (lb[u] < 0) continue;
-      if (lb[u] != cur) {
-        flush();
-        cur = lb[u];
-        if (C64P) {
-          const double2 ca = *reinterpret_cast<const double2*>(C64P + (size_t)cur * DP + 4 * m);
-          const double2 cb = *reinterpret_cast<const double2*>(C64P + (size_t)cur * DP + 4 * m + 2);
-          c0 = ca.x;
-          c1 = ca.y;
-          c2 = cb.x;
-          c3 = cb.y;
-        }
-      }
-      const double wr = wv[u];
-      a0 = fma(wr, (double)v[u].x, a0);
-      a1 = fma(wr, (double)v[u].y, a1);
-      a2 = fma(wr, (double)v[u].z, a2);
-      a3 = fma(wr, (double)v[u].w, a3);
-      aw += wr;
-      if (C64P) {  // padded features are 0 - 0
-        const double t0 = (double)v[u].x - c0, t1 = (double)v[u].y - c1;
-        const double t2 = (double)v[u].z - c2, t3 = (double)v[u].w - c3;
-        ss = fma(wr * t0, t0, ss);
-        ss = fma(wr * t1, t1, ss);
-        ss = fma(wr * t2, t2, ss);
-        ss = fma(wr * t3, t3, ss);
-      }
-    }
-  }
-  if (act) flush();
-  if (C64P) {
-    ss = wave_sum(ss);
-    if (lane == 0 && ss != 0.0) atomicAdd(sse, ss);
-  }
-}
-
 size_t sorted_stats_words(int64_t n, int k) { return 2 * (size_t)n + 3 * (size_t)k + 64; }
 
 // k_hist and k_scatter keep one 32-bit counter per cluster in LDS, 64 KiB of
@@ -4797,18 +4603,21 @@ static bool sort_fits(const Geometry& g) { return (size_t)g.k * 4 <= SORT_LDS; }
 // the range-tiled k_stats reads X once per LDS-sized cluster range; from three
 // ranges on, the sort (one gathered read of X plus ~5 bytes per row of
 // label/permutation traffic, and cursor atomics that contend when k is small)
-// is cheaper
-bool stats_needs_sort(const Geometry& g) {
+// is cheaper.  extra as stats_ranges: the weighted table row has one slot more.
+// (The diagnostic build's KM_SORT_MIN_RANGES moves the threshold of both
+// weightings; before the two functions were merged the weighted one was a
+// constant 3.  The product library uses 3 for both, as before.)
+bool stats_needs_sort(const Geometry& g, int extra) {
   static const int min_ranges = diag_env("KM_SORT_MIN_RANGES", 3);  // A/B knob
   if (g.dp > 256) return false;  // k_segsum holds a row in one wave-instruction
   if (!sort_fits(g)) return false;
   int fr = 0, kr = 0;
-  stats_ranges(g, &fr, &kr);
+  stats_ranges(g, &fr, &kr, extra);
   return kr == 0 || (g.k + kr - 1) / kr >= min_ranges;
 }
 
-// w != nullptr: the weighted segment sums (k_wsegsum) behind the same sort
-static hipError_t stats_sorted(const float* X, const Geometry& g, const int32_t* labels, const double* w,
+// w != nullptr: the weighted segment sums behind the same sort
+hipError_t launch_stats_sorted(const float* X, const Geometry& g, const int32_t* labels, const double* w,
                                double* stats, uint32_t* scratch, const double* C64P, int n_cu, const int* gate,
                                hipStream_t s) {
   if (g.n == 0) return hipSuccess;
@@ -4837,14 +4646,14 @@ static hipError_t stats_sorted(const float* X, const Geometry& g, const int32_t*
   int64_t wb = (int64_t)n_cu * 8;
   const unsigned grid = (unsigned)wb;
   double* sse = stats + (size_t)g.k * (g.d + 1);
-#define KM_SEGSUM(L)                                                                                              \
-  do {                                                                                                            \
-    if (w)                                                                                                        \
-      hipLaunchKernelGGL(k_wsegsum<L>, dim3(grid), dim3(256), 0, s, X, g.d, nsorted, perm, slab, w, stats, sse + 1, \
-                         C64P, sse, gate);                                                                        \
-    else                                                                                                          \
-      hipLaunchKernelGGL(k_segsum<L>, dim3(grid), dim3(256), 0, s, X, g.d, nsorted, perm, slab, stats, C64P, sse,  \
-                         gate);                                                                                   \
+#define KM_SEGSUM(L)                                                                                               \
+  do {                                                                                                             \
+    if (w)                                                                                                         \
+      hipLaunchKernelGGL((k_segsum<L, true>), dim3(grid), dim3(256), 0, s, X, g.d, nsorted, perm, slab, stats, C64P, \
+                         sse, gate, w, sse + 1);                                                                   \
+    else                                                                                                           \
+      hipLaunchKernelGGL((k_segsum<L, false>), dim3(grid), dim3(256), 0, s, X, g.d, nsorted, perm, slab, stats,     \
+                         C64P, sse, gate, w, sse + 1);                                                             \
   } while (0)
   switch (g.dp / 4) {
     case 4: KM_SEGSUM(4); break;
@@ -4859,26 +4668,6 @@ static hipError_t stats_sorted(const float* X, const Geometry& g, const int32_t*
   }
 #undef KM_SEGSUM
   return hipGetLastError();
-}
-
-hipError_t launch_stats_sorted(const float* X, const Geometry& g, const int32_t* labels, double* stats,
-                               uint32_t* scratch, const double* C64P, int n_cu, const int* gate, hipStream_t s) {
-  return stats_sorted(X, g, labels, nullptr, stats, scratch, C64P, n_cu, gate, s);
-}
-
-// the weighted statistics' table row has one slot more (stats_ranges extra = 2)
-bool wstats_needs_sort(const Geometry& g) {
-  if (g.dp > 256 || !sort_fits(g)) return false;
-  int fr = 0, kr = 0;
-  stats_ranges(g, &fr, &kr, 2);
-  return kr == 0 || (g.k + kr - 1) / kr >= 3;
-}
-
-hipError_t launch_wstats_sorted(const float* X, const Geometry& g, const int32_t* labels, const double* w,
-                                double* stats, uint32_t* scratch, const double* C64P, int n_cu, const int* gate,
-                                hipStream_t s) {
-  if (!w) return hipErrorInvalidValue;
-  return stats_sorted(X, g, labels, w, stats, scratch, C64P, n_cu, gate, s);
 }
 
 // ---------------------------------------------------------------------------

@@ -572,11 +572,41 @@ bool use_s1(km_ctx* c, bool with_stats) {
 
 // the statistics pass of a full-statistics km_assign_stats (km_stats_route):
 // 0 inside the assign kernel, 1 the range-tiled table, 2 the counting sort.
-// run_assign and run_assign_weighted choose their pass by it
+// run_stats chooses its pass by it
 int stats_route(const km_ctx* c) {
-  if (c->w) return km::wstats_needs_sort(c->g) ? 2 : 1;
+  if (c->w) return km::stats_needs_sort(c->g, 2) ? 2 : 1;
   if (c->path == 1 || c->fused) return 0;
-  return km::stats_needs_sort(c->g) ? 2 : 1;
+  return km::stats_needs_sort(c->g, 1) ? 2 : 1;
+}
+
+// the statistics pass over X by stats_route (1 or 2), weighted where the
+// context holds weights; sse: the SSE residuals in the same pass
+int run_stats(km_ctx* c, bool sse) {
+  const km::Geometry& g = c->g;
+  ProfScope ps(c, KM_K_STATS);
+  if (stats_route(c) == 2) {
+    const size_t words = km::sorted_stats_words(g.n, g.k);
+    if (words > c->sort_words) {
+      dfree(c->sort_scratch);
+      KM_HIP(hipMalloc(&c->sort_scratch, sizeof(uint32_t) * words));
+      c->sort_words = words;
+    }
+    // (path 1 keeps no padded float64 image: its geometries never sort)
+    KM_REQUIRE(!c->w || c->path == 2, KM_ERR_UNSUPPORTED,
+               "km_assign_stats: weighted statistics need the MFMA path at this k");
+    KM_HIP(km::launch_stats_sorted(c->X, g, c->labels, c->w, c->stats, c->sort_scratch, sse ? c->C64P : nullptr,
+                                   c->n_cu, c->gate, c->stream));
+  } else {
+    // SSE residuals in the same pass over X (feature-range tiles).  The small
+    // path keeps no padded float64 image: its centroids are [k][d].  Only the
+    // weighted pass comes here on it (run_assign returns before, and
+    // launch_stats refuses an unweighted stride other than dp)
+    const bool small = c->path == 1;
+    KM_HIP(km::launch_stats(c->X, g, c->labels, c->w, c->stats, c->n_cu, c->gate, c->stream,
+                            sse ? (small ? c->C64_cur : c->C64P) : nullptr, small ? g.d : g.dp,
+                            sse ? c->C32 : nullptr));
+  }
+  return KM_OK;
 }
 
 // before an update reads the statistics: delta -> fold into the full sums;
@@ -803,23 +833,7 @@ int run_assign(km_ctx* c, bool with_stats) {
     return KM_OK;
   }
   }
-  if (with_stats) {
-    ProfScope ps(c, KM_K_STATS);
-    if (stats_route(c) == 2) {
-      const size_t words = km::sorted_stats_words(g.n, g.k);
-      if (words > c->sort_words) {
-        dfree(c->sort_scratch);
-        KM_HIP(hipMalloc(&c->sort_scratch, sizeof(uint32_t) * words));
-        c->sort_words = words;
-      }
-      KM_HIP(km::launch_stats_sorted(c->X, g, c->labels, c->stats, c->sort_scratch, sse ? c->C64P : nullptr,
-                                     c->n_cu, c->gate, c->stream));
-    } else {
-      // SSE residuals in the same pass over X (feature-range tiles)
-      KM_HIP(km::launch_stats(c->X, g, c->labels, c->stats, c->n_cu, c->gate, c->stream, sse ? c->C64P : nullptr,
-                              sse ? c->C32 : nullptr));
-    }
-  }
+  if (with_stats) return run_stats(c, sse);
   return KM_OK;
 }
 
@@ -827,7 +841,6 @@ int run_assign(km_ctx* c, bool with_stats) {
 // takes, then the weighted statistics pass (X is read twice per iteration).
 // Always full sums: nothing of the delta machinery survives the pass
 int run_assign_weighted(km_ctx* c) {
-  const km::Geometry& g = c->g;
   int rc = run_assign(c, false);
   if (rc != KM_OK) return rc;
   c->delta_ready = false;  // the labels are this pass's, stats_full describes none
@@ -838,26 +851,7 @@ int run_assign_weighted(km_ctx* c) {
   c->gate_init_dev = nullptr;
   KM_HIP(hipMemsetAsync(c->stats, 0, sizeof(double) * stats_len(c), c->stream));
   c->stats_clean = false;
-  const bool sse = c->want_sse;
-  ProfScope ps(c, KM_K_STATS);
-  if (stats_route(c) == 2) {
-    const size_t words = km::sorted_stats_words(g.n, g.k);
-    if (words > c->sort_words) {
-      dfree(c->sort_scratch);
-      KM_HIP(hipMalloc(&c->sort_scratch, sizeof(uint32_t) * words));
-      c->sort_words = words;
-    }
-    // (path 1 keeps no padded float64 image: its geometries never sort)
-    KM_REQUIRE(c->path == 2, KM_ERR_UNSUPPORTED, "km_assign_stats: weighted statistics need the MFMA path at this k");
-    KM_HIP(km::launch_wstats_sorted(c->X, g, c->labels, c->w, c->stats, c->sort_scratch, sse ? c->C64P : nullptr,
-                                    c->n_cu, c->gate, c->stream));
-  } else {
-    // the small path keeps no padded float64 image: its centroids are [k][d]
-    const double* c64 = c->path == 1 ? c->C64_cur : c->C64P;
-    KM_HIP(km::launch_wstats(c->X, g, c->labels, c->w, c->stats, c->n_cu, c->gate, c->stream, sse ? c64 : nullptr,
-                             c->path == 1 ? g.d : g.dp, sse ? c->C32 : nullptr));
-  }
-  return KM_OK;
+  return run_stats(c, c->want_sse);
 }
 
 // the update's divisor: the clusters' sums of weights behind the SSE slot of

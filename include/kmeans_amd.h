@@ -114,8 +114,8 @@ int km_gated_rows(km_ctx* ctx, int64_t* out);
 /* Which statistics pass the next km_assign_stats with FULL statistics runs
  * for the current geometry and weight mode (read-only; needs centroids):
  *   *route = 0  inside the assign kernel (small path, fused path);
- *            1  the range-tiled LDS table (k_stats; weighted k_wstats);
- *            2  the counting sort and segment sums (k_segsum / k_wsegsum).
+ *            1  the range-tiled LDS table (k_stats, weighted or not);
+ *            2  the counting sort and segment sums (k_segsum, weighted or not).
  * For routes 1 and 2 the split of the table: *fr features and *kr clusters
  * per workgroup, *feature_ranges = dp / fr and *cluster_ranges =
  * ceil(k / kr) of them (route 2 sorts because the table would need that

@@ -3,8 +3,8 @@
     python scripts/weighted_time.py --config c3 [--reps 12] [--steps 20]
 
 With ``fit(..., sample_weight=w)`` an iteration is: the labels-only
-assignment, then one weighted statistics pass over the rows (k_wstats, or the
-counting sort + k_wsegsum).  Per config this times, with HIP events around
+assignment, then one weighted statistics pass over the rows (k_stats<SSE, true>, or the
+counting sort + k_segsum<L, true>).  Per config this times, with HIP events around
 the statistics phase (km_profile, KM_K_STATS), after warm-up and over
 ``--reps`` repeats of the same assignment (median, min, max reported):
 

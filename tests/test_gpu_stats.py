@@ -2,9 +2,9 @@
 counts, SSE and sums of weights (reduceByKey + the SSE map of
 kmeans_spark.py:169-173 and :224-237), bit for bit under skewed labels.
 
-The kernels: k_stats<SSE> / k_wstats<SSE> (an LDS table tiled over cluster
+The kernels: k_stats<SSE, W> (W: weighted; an LDS table tiled over cluster
 and feature ranges), the counting-sort route (k_hist, k_scan, k_scatter,
-k_put_counts, k_segsum<L> / k_wsegsum<L> for eight row widths), and the
+k_put_counts, k_segsum<L, W> for eight row widths), and the
 tables the fused screen and k_rerank2 flush.  The inputs are planted integer
 data (tests/stats_data.py; tests/test_host_stats_data.py proves their
 properties without a GPU): every sum is an integer far below 2^53, so every
