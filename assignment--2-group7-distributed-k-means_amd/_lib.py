@@ -26,6 +26,10 @@ HEADER = os.path.join(ROOT, "include", "kmeans_amd.h")
 KM_ABI_VERSION = 6
 KM_OK = 0
 KM_EMPTY = 1
+KM_ERR_ARG, KM_ERR_HIP, KM_ERR_STATE, KM_ERR_UNSUPPORTED = -1, -2, -3, -4
+
+# element types of km_load_device's source (KM_DT_*)
+KM_DT_F32, KM_DT_F64, KM_DT_F16, KM_DT_BF16 = range(4)
 
 KM_K_ASSIGN, KM_K_RESOLVE, KM_K_STATS, KM_K_UPDATE, KM_K_PREP, KM_K_SEED = range(6)
 KERNEL_KINDS = {"assign": KM_K_ASSIGN, "resolve": KM_K_RESOLVE, "stats": KM_K_STATS, "update": KM_K_UPDATE,
@@ -72,6 +76,7 @@ SIGNATURES = {
     "km_stats_route": [_P, _PI32, _PI32, _PI32, _PI32, _PI32],
     "km_load_begin": [_P, _I64, _I32],
     "km_load_rows": [_P, _I64, _PF, _I64],
+    "km_load_device": [_P, _I64, _P, _I64, _I64, _I32],
     "km_generate_blobs": [_P, _I64, _I32, _I64, _I32, ctypes.c_float, ctypes.c_float, ctypes.c_uint64],
     "km_set_weights": [_P, _I64, _PD, _I64],
     "km_clear_weights": [_P],
@@ -106,6 +111,7 @@ SIGNATURES = {
     "km_seed_end": [_P],
     "km_predict": [_P, _PI32],
     "km_labels": [_P, _PI32],
+    "km_labels_device": [_P, _P],
     "km_profile": [_P, _I32],
     "km_profile_every": [_P, _I32],
     "km_prof_read": [_P, _I32, _PD, _PI64],

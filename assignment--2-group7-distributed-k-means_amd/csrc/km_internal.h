@@ -84,6 +84,15 @@ hipError_t launch_prep_small(const double* C64, const Geometry& g, float* C32, f
 hipError_t launch_prep_split(const float* C32, const Geometry& g, const double* cn2, const float* xabs,
                              const float* cabs, _Float16* Chi, _Float16* Clo, float* cn2s, const int* gate, hipStream_t s);
 hipError_t launch_absmax(const float* X, int64_t nfloats, float* out, hipStream_t s);
+// km_ingest.hip: rows already in HBM (row-major [nrows][g.d] of KM_DT_* elements,
+// row stride src_stride elements) converted into X (float32, stride g.dp, the
+// padding columns written as 0).  The caller has checked that src is device
+// memory.  ingest_elem_size: bytes of a KM_DT_* element, 0 for an unknown code;
+// ingest_vec: the aligned instance (one vector load per group of 4) applies
+hipError_t launch_ingest(const void* src, int dtype, int64_t src_stride, int64_t nrows, const Geometry& g, float* X,
+                         int n_cu, hipStream_t s);
+int ingest_elem_size(int dtype);
+bool ingest_vec(const void* src, int64_t src_stride, int elem_size);
 // Small k*d path: direct-form fp32 screening (ambiguous rows queued, see below),
 // optional fused statistics (LDS float64 table, replicated per lane).
 // want_sse: also add every point's float64 residual ||x - c_label||^2 to

@@ -1083,6 +1083,82 @@ int km_load_rows(km_ctx* c, int64_t row0, const float* rows, int64_t nrows) {
   return KM_OK;
 }
 
+// [p, p + bytes) as the caller describes it must lie inside ONE device
+// allocation of the context's GPU, so that a wrong pointer, stride or row
+// count is an error code and never a fault in a kernel or a copy: the pointer
+// is looked up (hipPointerGetAttributes), then the allocation that holds it
+// (hipMemGetAddressRange) must hold the whole range
+static int require_device_range(km_ctx* c, const void* p, uint64_t bytes, const char* what) {
+  hipPointerAttribute_t at{};
+  const hipError_t e = hipPointerGetAttributes(&at, p);
+  if (e != hipSuccess) (void)hipGetLastError();  // an unknown pointer: not a sticky error
+  if (e != hipSuccess || at.type != hipMemoryTypeDevice)
+    return fail(KM_ERR_ARG, std::string(what) + ": the pointer is not device memory (the context is on device " +
+                                std::to_string(c->device) + ", the pointer is on none)");
+  if (at.device != c->device)
+    return fail(KM_ERR_ARG, std::string(what) + ": the pointer is memory of device " + std::to_string(at.device) +
+                                ", the context is on device " + std::to_string(c->device));
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  const hipError_t er = hipMemGetAddressRange(&base, &size, const_cast<void*>(p));
+  bool inside;
+  if (er == hipSuccess) {
+    const uint64_t lo = (uint64_t)(uintptr_t)base, q = (uint64_t)(uintptr_t)p;
+    inside = q >= lo && bytes <= (uint64_t)size && q - lo <= (uint64_t)size - bytes;
+  } else {
+    // memory the runtime reports no single range for (mapped in pieces): the
+    // last byte at least must be device memory of this GPU as well
+    (void)hipGetLastError();
+    hipPointerAttribute_t end{};
+    const hipError_t ee = hipPointerGetAttributes(&end, static_cast<const char*>(p) + (bytes ? bytes - 1 : 0));
+    if (ee != hipSuccess) (void)hipGetLastError();
+    inside = ee == hipSuccess && end.type == hipMemoryTypeDevice && end.device == c->device;
+  }
+  if (!inside)
+    return fail(KM_ERR_ARG, std::string(what) + ": the range of " + std::to_string(bytes) +
+                                " bytes runs past the end of the device allocation that holds the pointer");
+  return KM_OK;
+}
+
+int km_load_device(km_ctx* c, int64_t row0, const void* dev_rows, int64_t nrows, int64_t src_stride_elems,
+                   int32_t dtype) {
+  KM_REQUIRE(c && c->loaded, KM_ERR_STATE, "km_load_device: call km_load_begin first");
+  KM_REQUIRE(row0 >= 0 && nrows >= 0 && row0 + nrows <= c->g.n, KM_ERR_ARG, "km_load_device: rows out of range");
+  const int esz = km::ingest_elem_size(dtype);
+  KM_REQUIRE(esz != 0, KM_ERR_ARG, "km_load_device: unknown dtype " + std::to_string(dtype));
+  if (nrows == 0) return KM_OK;
+  KM_REQUIRE(dev_rows, KM_ERR_ARG, "km_load_device: null rows");
+  const int d = c->g.d, dp = c->g.dp;
+  KM_REQUIRE(src_stride_elems >= d, KM_ERR_ARG, "km_load_device: row stride shorter than a row");
+  int64_t span = 0;  // elements from the first one read to the last
+  KM_REQUIRE(!__builtin_mul_overflow(nrows - 1, src_stride_elems, &span) && !__builtin_add_overflow(span, (int64_t)d, &span) &&
+                 span <= INT64_MAX / esz,
+             KM_ERR_ARG, "km_load_device: row stride out of range");
+  KM_HIP(hipSetDevice(c->device));
+  {
+    const int rcp = require_device_range(c, dev_rows, (uint64_t)span * (uint64_t)esz, "km_load_device");
+    if (rcp != KM_OK) return rcp;
+  }
+  {
+    const int rcf = flush_assign(c);  // it must read the rows it was called for
+    if (rcf != KM_OK) return rcf;
+  }
+  c->delta_ready = false;  // the rows behind the labels change
+  c->bounds_valid = false;
+  float* dst = c->X + row0 * dp;
+  {
+    ProfScope ps(c, KM_K_PREP);  // the conversion alone (scripts/ingest_time.py)
+    KM_HIP(km::launch_ingest(dev_rows, dtype, src_stride_elems, nrows, c->g, dst, c->n_cu, c->stream));
+  }
+  // the data maximum and the row norms from the stored rows, as km_load_rows
+  KM_HIP(km::launch_absmax(dst, nrows * dp, c->xabs, c->stream));
+  km::Geometry sub = c->g;
+  sub.n = nrows;
+  KM_HIP(km::launch_row_norm(dst, sub, c->xnorm + row0, c->stream));
+  KM_HIP(hipStreamSynchronize(c->stream));
+  return KM_OK;
+}
+
 // a change of mode (weights set <-> none) changes the length of the stats
 // buffer and what the statistics in flight mean
 static int weights_mode_changed(km_ctx* c) {
@@ -1829,6 +1905,24 @@ int km_labels(km_ctx* c, int32_t* labels_out) {
   }
   if (c->g.n > 0)
     KM_HIP(hipMemcpyAsync(labels_out, c->labels, sizeof(int32_t) * c->g.n, hipMemcpyDeviceToHost, c->stream));
+  KM_HIP(hipStreamSynchronize(c->stream));
+  return KM_OK;
+}
+
+int km_labels_device(km_ctx* c, int32_t* dev_out) {
+  KM_REQUIRE(c && c->loaded, KM_ERR_STATE, "km_labels_device: no data");
+  if (c->g.n == 0) return KM_OK;
+  KM_REQUIRE(dev_out, KM_ERR_ARG, "km_labels_device: null destination");
+  KM_HIP(hipSetDevice(c->device));
+  {
+    const int rcp = require_device_range(c, dev_out, sizeof(int32_t) * (uint64_t)c->g.n, "km_labels_device");
+    if (rcp != KM_OK) return rcp;
+  }
+  {
+    const int rcf = flush_assign(c);
+    if (rcf != KM_OK) return rcf;
+  }
+  KM_HIP(hipMemcpyAsync(dev_out, c->labels, sizeof(int32_t) * c->g.n, hipMemcpyDeviceToDevice, c->stream));
   KM_HIP(hipStreamSynchronize(c->stream));
   return KM_OK;
 }

@@ -8,6 +8,10 @@ The reference receives a PySpark RDD of ``(d,)`` float arrays built by
   (``LocalContext().parallelize(X, numSlices)`` mirrors ``sc.parallelize``),
 * a real PySpark RDD (anything with ``mapPartitions`` / ``mapPartitionsWithIndex``),
 * a NumPy array ``[n][d]`` (one partition),
+* a ``torch.Tensor`` ``[n][d]`` (one partition, like the array): on the GPU
+  its rows never visit the host (``Placement.device_rows``, a view; the
+  engine converts float16 / bfloat16 / float32 / float64 to the float32 row
+  store in HBM), on the CPU it takes the array's route,
 * ``DeviceBlobs`` — a synthetic Gaussian-blob dataset generated directly in
   HBM (benchmarks; nothing on the host).
 
@@ -37,6 +41,7 @@ rounded row.
 from __future__ import annotations
 
 import itertools
+import sys
 from dataclasses import dataclass
 from typing import Any, List, Optional, Sequence, Tuple
 
@@ -170,6 +175,43 @@ class Placement:
     d: int
     dtype: Any
     blobs: Optional[DeviceBlobs] = None
+    # this rank's rows as a view of a GPU tensor (no copy; local_rows is then None).  The view shares the
+    # caller's storage: LloydRunner.load drops it once the rows are in the row store
+    device_rows: Any = None
+
+
+def is_tensor(x) -> bool:
+    """A ``torch.Tensor``, without importing torch here: whoever holds a
+    tensor has imported it."""
+    torch = sys.modules.get("torch")
+    return torch is not None and isinstance(x, torch.Tensor)
+
+
+def _tensor_dtype(t):
+    """The NumPy dtype a tensor's rows count as: float64 stays, the narrower
+    floats (bfloat16 has no NumPy dtype) are float32, integers and bool stay
+    non-floating (``place`` makes them float64, as for an integer ndarray)."""
+    torch = sys.modules["torch"]
+    if t.dtype.is_complex:
+        raise TypeError(f"unsupported dataset type {type(t).__name__} of dtype {t.dtype}: expected real rows")
+    if t.dtype == torch.float64:
+        return np.dtype(np.float64)
+    if t.dtype.is_floating_point:
+        return np.dtype(np.float32)
+    return np.dtype(np.int64)
+
+
+def tensor_to_host(t) -> np.ndarray:
+    """A tensor's rows as an ndarray for the host route: float16, float32 and
+    float64 as they are, bfloat16 widened to float32, integers and bool
+    through float64."""
+    torch = sys.modules["torch"]
+    t = t.detach()
+    if t.dtype == torch.bfloat16:
+        t = t.to(torch.float32)
+    elif not t.dtype.is_floating_point:
+        t = t.to(torch.float64)
+    return t.cpu().numpy()
 
 
 def _count_width(it):
@@ -189,6 +231,10 @@ def _layout(rdd) -> Tuple[List[int], Optional[int], Any]:
         if rdd.ndim != 2:
             raise ValueError("input array must be 2-D [n][d]")
         return [rdd.shape[0]], (rdd.shape[1] if rdd.shape[0] else None), rdd.dtype
+    if is_tensor(rdd):                                         # the ndarray's layout: one partition of N rows
+        if rdd.dim() != 2:
+            raise ValueError("input tensor must be 2-D [n][d]")
+        return [rdd.shape[0]], (rdd.shape[1] if rdd.shape[0] and rdd.shape[1] else None), _tensor_dtype(rdd)
     if isinstance(rdd, LocalRDD):
         sizes = [rdd.partition_len(i) for i in range(rdd.getNumPartitions())]
         for i, n in enumerate(sizes):
@@ -205,7 +251,7 @@ def _layout(rdd) -> Tuple[List[int], Optional[int], Any]:
                 return sizes, int(width), np.dtype(kind)
         return sizes, None, np.float64
     raise TypeError(f"unsupported dataset type {type(rdd).__name__}: expected an RDD, LocalRDD, "
-                    f"ndarray or DeviceBlobs")
+                    f"ndarray, torch.Tensor or DeviceBlobs")
 
 
 def _segments(sizes: Sequence[int], a: int, b: int) -> List[Tuple[int, int, int]]:
@@ -224,6 +270,8 @@ def _own_rows(rdd, segs: List[Tuple[int, int, int]], d: int) -> np.ndarray:
     materialised / transferred."""
     if isinstance(rdd, np.ndarray):
         return np.concatenate([rdd[lo:hi] for _, lo, hi in segs]) if segs else np.zeros((0, d))
+    if is_tensor(rdd):                                         # one partition: at most one piece
+        return tensor_to_host(rdd[segs[0][1]:segs[0][2]]) if segs else np.zeros((0, d))
     if isinstance(rdd, LocalRDD):
         mine = []
         for i, lo, hi in segs:
@@ -268,6 +316,14 @@ def place(rdd, comm) -> Placement:
     # balanced row blocks across partition boundaries (the takeSample layout
     # stays the dataset's partitions)
     a, b = rank_rows(int(sum(sizes)), comm.world, comm.rank)
+    if is_tensor(rdd) and rdd.is_cuda:
+        # rows already in HBM stay there: the rank's slice as a view (every
+        # rank passes the whole dataset, as with an ndarray)
+        rows = rdd.detach()[a:b]
+        if not rows.dtype.is_floating_point:
+            rows = rows.to(sys.modules["torch"].float64)
+        return Placement(global_sizes=sizes, local_rows=None, row0=a, n_local=b - a, n_global=int(sum(sizes)),
+                         d=d, dtype=np.dtype(dtype), device_rows=rows)
     local = _own_rows(rdd, _segments(sizes, a, b), d)
     row0 = a
     if local.ndim != 2:

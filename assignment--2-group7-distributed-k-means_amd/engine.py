@@ -87,6 +87,56 @@ class HipEngine:
         self._rep_mode, self._rep_t = 0, None   # ... and the takeSample layout (set_layout again)
         return n
 
+    def load_device(self, t) -> int:
+        """This rank's rows from a 2-D torch tensor on ``cuda:<self.device>``
+        (float16, bfloat16, float32 or float64): converted to the float32 row
+        store on the GPU (km_load_device), no host copy.  Row-strided views
+        (unit column stride, row stride >= d, any storage offset) are read in
+        place; a tensor with another column stride or overlapping rows is made
+        contiguous first (one device copy).  The tensor's current stream is
+        synchronised before the load, which runs on the engine's own stream;
+        the tensor may be freed or overwritten once this returns."""
+        import torch
+        if t.dim() != 2:
+            raise ValueError("rows must be a 2-D tensor")
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError(f"the tensor is on {t.device}, the engine on cuda:{self.device}")
+        code = {torch.float32: _lib.KM_DT_F32, torch.float64: _lib.KM_DT_F64, torch.float16: _lib.KM_DT_F16,
+                torch.bfloat16: _lib.KM_DT_BF16}.get(t.dtype)
+        if code is None:
+            raise TypeError(f"load_device takes float16, bfloat16, float32 or float64 rows, not {t.dtype}")
+        t = t.detach()
+        n, d = t.shape
+        if d <= 0:
+            raise ValueError("rows must have at least one column")
+        # (the stride of a dimension of size 1 means nothing)
+        if (d > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < d):
+            t = t.contiguous()
+        stride = t.stride(0) if n > 1 else d
+        torch.cuda.current_stream(t.device).synchronize()      # the library reads on its own stream
+        self._c(self.lib.km_load_begin(self.ctx, n, d), "km_load_begin")
+        if n:
+            self._c(self.lib.km_load_device(self.ctx, 0, ctypes.c_void_p(t.data_ptr()), n, stride, code),
+                    "km_load_device")
+        self.n, self.d = n, d
+        self.weighted = False
+        self._stats_t = None
+        self._rep_mode, self._rep_t = 0, None
+        return n
+
+    def labels_tensor(self):
+        """The labels of the last assignment (``predict_device``) as a fresh
+        ``torch.int32`` tensor [n] on the engine's GPU (km_labels_device: a
+        device-to-device copy, nothing reaches the host)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        out = torch.empty(self.n, dtype=torch.int32, device=dev)
+        if self.n:
+            # the block may be one torch freed with work still queued on its stream
+            torch.cuda.current_stream(dev).synchronize()
+            self._c(self.lib.km_labels_device(self.ctx, ctypes.c_void_p(out.data_ptr())), "km_labels_device")
+        return out
+
     def load_weights(self, w) -> None:
         """This rank's row weights (float64 [n], finite and > 0: the caller
         validates), or None for none.  Weighted mode: km_assign_stats computes

@@ -27,7 +27,7 @@ import numpy as np
 
 from . import _lib, sampling, seeding
 from .comm import Communicator
-from .dataset import DeviceBlobs, EmptyDataset, LocalRDD, Placement, place
+from .dataset import DeviceBlobs, EmptyDataset, LocalRDD, Placement, is_tensor, place, tensor_to_host
 from .engine import make_engine
 
 
@@ -46,6 +46,7 @@ class LloydRunner:
         self.host_ms = None      # {call kind: host wall ms} while a caller times run() (bench.py)
         # takeSample's Bernoulli pass on the GPU when the engine has one
         self.sampler = getattr(engine, "bernoulli", None)
+        self.from_device = False  # the rows were loaded from a GPU tensor (predict then leaves the labels in HBM)
 
     # -- set-up --------------------------------------------------------------------
     def load(self) -> None:
@@ -53,6 +54,17 @@ class LloydRunner:
         if pl.blobs is not None:
             b = pl.blobs
             self.engine.load_blobs(pl.n_local, b.d, pl.row0, b.n_centers, b.box, b.std, b.seed)
+        elif pl.device_rows is not None:
+            # a GPU tensor: converted in HBM; an engine without that entry
+            # (the tests' CPU engine) gets the host copy of the slice
+            if hasattr(self.engine, "load_device"):
+                self.engine.load_device(pl.device_rows)
+            else:
+                self.engine.load_host(tensor_to_host(pl.device_rows))
+            # the rows are in the row store: let the view go, so that the
+            # caller's tensor is freed when the caller drops it
+            self.from_device = True
+            pl.device_rows = None
         else:
             self.engine.load_host(pl.local_rows)
         # empty clusters are repaired on the device (takeSample policy,
@@ -251,15 +263,36 @@ class LabelsRDD(LocalRDD):
       ``mapPartitions``, ``partition_array`` ...) run without communication
       on this rank's shard (one partition), or on every label once
       ``collect(everywhere=True)`` gathered them; with one rank that is the
-      whole result."""
+      whole result;
+    * ``to_tensor()`` is this rank's shard as a ``torch.int32`` tensor.  When
+      ``predict`` ran on a GPU tensor the labels were left in HBM and this is
+      that device tensor: no host copy is ever made for it, and the host array
+      behind every other method is materialised at its first use (``count()``
+      needs none).  For any other input it wraps ``local()`` on the CPU."""
 
-    def __init__(self, local_labels: np.ndarray, comm: Communicator, everywhere: bool = False):
-        self._local = local_labels
+    def __init__(self, local_labels, comm: Communicator, everywhere: bool = False):
+        # an ndarray, or a device tensor whose host copy is made on demand
+        self._dev = local_labels if is_tensor(local_labels) else None
+        self._host = None if self._dev is not None else local_labels
         self._comm = comm
         self._everywhere = everywhere
         self._all = None     # every rank's labels (everywhere)
         self._root = None    # the driver's copy (rank 0)
         super().__init__([])
+
+    @property
+    def _local(self) -> np.ndarray:
+        if self._host is None:
+            self._host = self._dev.cpu().numpy()
+        return self._host
+
+    def to_tensor(self):
+        """This rank's labels as a ``torch.int32`` tensor: on the GPU where
+        ``predict`` left them there, else a CPU tensor over ``local()``."""
+        if self._dev is not None:
+            return self._dev
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(self._local, dtype=np.int32))
 
     @property
     def _parts(self):
@@ -290,9 +323,10 @@ class LabelsRDD(LocalRDD):
         return self._gather(everywhere).tolist()
 
     def count(self) -> int:
+        n_local = len(self._host) if self._host is not None else int(self._dev.numel())
         if self._comm.world > 1:
-            return int(self._comm.allreduce_np(np.array([float(len(self._local))]))[0])
-        return int(len(self._local))
+            return int(self._comm.allreduce_np(np.array([float(n_local)]))[0])
+        return n_local
 
     def getNumPartitions(self) -> int:
         return self._comm.world
@@ -341,7 +375,14 @@ class KMeans:
     therefore the reference's result on ``X.astype(float32)``: identical for
     float32-representable data, within float32 rounding (~1e-7 relative of the
     data scale) of the reference on raw float64 rows.  Centroids are returned
-    in the input's float dtype."""
+    in the input's float dtype.
+
+    Inputs: an RDD, ``LocalRDD``, ndarray, ``DeviceBlobs`` or a 2-D
+    ``torch.Tensor``.  A tensor on the GPU (float16, bfloat16, float32,
+    float64) is converted into the row store in HBM, with the same rounding
+    and without a host copy, and ``predict`` leaves its labels there
+    (``LabelsRDD.to_tensor()``); centroids are float64 ndarrays for a float64
+    tensor and float32 ones for the narrower floats."""
 
     _engine_factory = None  # test seam: tests/ inject a CPU engine for host-logic tests
 
@@ -395,8 +436,14 @@ class KMeans:
 
     def _make_runner(self, rdd, comm: Communicator) -> LloydRunner:
         pl = place(rdd, comm)
-        factory = type(self)._engine_factory or make_engine
-        eng = factory(comm)
+        factory = type(self)._engine_factory
+        if factory is not None:
+            eng = factory(comm)
+        elif pl.device_rows is not None and comm.world == 1:
+            eng = make_engine(comm, pl.device_rows.device.index)   # the tensor's GPU: it is not moved
+        else:
+            # several ranks: each on its own GPU; a tensor elsewhere is refused by load_device
+            eng = make_engine(comm)
         run = LloydRunner(eng, pl, comm, self.k)
         run.load()
         return run
@@ -421,6 +468,9 @@ class KMeans:
     def _check_weights(sample_weight, n_total: int) -> np.ndarray:
         """sample_weight as float64 [n_total]: finite and strictly positive (a
         cluster is then empty exactly when it holds no row)."""
+        if is_tensor(sample_weight):
+            # converted on the host (N x 8 bytes); the weights have no device route
+            sample_weight = sample_weight.detach().to(sys.modules["torch"].float64).cpu().numpy()
         w = np.asarray(sample_weight, dtype=np.float64)
         if w.ndim != 1 or len(w) != n_total:
             raise ValueError(f"sample_weight has length {len(w) if w.ndim == 1 else w.shape}, "
@@ -432,7 +482,8 @@ class KMeans:
     # -- public API ----------------------------------------------------------------------
     def fit(self, rdd, sc=None, *, sample_weight=None) -> "KMeans":
         """``sample_weight``: one weight per row in global row order (every
-        rank passes the whole array), or None.  Labels are unchanged; a
+        rank passes the whole array; a tensor is converted on the host), or
+        None.  Labels are unchanged; a
         cluster's new centroid is sum(w x) / sum(w) over its rows, the SSE
         sum(w ||x - c||^2); cluster sizes, the empty-cluster policy and
         ``init="random"`` (takeSample) ignore the weights."""
@@ -470,6 +521,12 @@ class KMeans:
         return self
 
     def predict(self, rdd, sc=None):
+        """Labels of ``rdd``'s rows as a ``LabelsRDD``.  Predicting on the very
+        object ``fit`` was given reuses the rows resident in HBM; as with an
+        ndarray, a tensor mutated in place between ``fit`` and ``predict``
+        therefore still predicts on the rows as they were loaded.  For a GPU
+        tensor the labels stay in HBM (``LabelsRDD.to_tensor()``) until a
+        host-side method asks for them."""
         if self.centroids is None:
             raise ValueError("Model must be fitted before prediction")
         comm = Communicator()
@@ -481,6 +538,9 @@ class KMeans:
             except EmptyDataset:
                 return LabelsRDD(np.zeros(0, dtype=np.int32), comm)  # a lazy map over no rows (L350)
         run.engine.set_centroids(np.asarray(self.centroids, dtype=np.float64))
+        if run.from_device and hasattr(run.engine, "labels_tensor"):
+            run.engine.predict_device()                        # the labels stay in HBM
+            return LabelsRDD(run.engine.labels_tensor(), comm)
         labels = LabelsRDD(run.engine.predict(), comm)
         if sc is not None and hasattr(sc, "_jsc") and hasattr(rdd, "getNumPartitions"):
             # a real SparkContext (every rank's driver program parallelizes the whole list)

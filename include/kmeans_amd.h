@@ -132,6 +132,38 @@ int km_stats_route(km_ctx* ctx, int32_t* route, int32_t* cluster_ranges, int32_t
  * [row0, row0 + nrows) (pinned staging, chunked). */
 int km_load_begin(km_ctx* ctx, int64_t n, int32_t d);
 int km_load_rows(km_ctx* ctx, int64_t row0, const float* rows, int64_t nrows);
+/* The device-source twin of km_load_rows (a torch tensor already in HBM):
+ * dev_rows is a row-major [nrows][d] array of dtype elements in device memory
+ * of the context's GPU, row stride src_stride_elems >= d elements, unit column
+ * stride; any base alignment (an aligned base and row stride select the
+ * vector-load instance of the kernel).  One kernel (k_ingest, km_ingest.hip)
+ * converts the rows into the row store: fp16 and bf16 widen exactly, fp64
+ * rounds to nearest-even as the host route's conversion to float32 does (out
+ * of range -> +-inf, NaN stays NaN, the sign of zero is kept, subnormals are
+ * rounded, not flushed), so the stored rows, and the data maximum and row
+ * norms computed from them, hold the bits a km_load_rows of the same float32
+ * values leaves.  Like km_load_rows it flushes a deferred assign, invalidates
+ * delta statistics and the row gate, runs on the context's stream and
+ * synchronises it before returning: the caller may then free or overwrite the
+ * source, and must itself have finished the work that produced it (the
+ * context's stream is not ordered after any other).
+ * KM_ERR_STATE before km_load_begin; KM_ERR_ARG for rows out of range, an
+ * unknown dtype, src_stride_elems < d, a null pointer with nrows > 0, a
+ * pointer that hipPointerGetAttributes does not report as device memory of
+ * the context's GPU (the message names both devices), and a source, from its
+ * first byte to the last one of the last row, that does not lie inside the
+ * one device allocation holding the pointer (hipMemGetAddressRange; where the
+ * runtime reports no single range, the last byte is looked up like the
+ * first): a wrong pointer, stride or row count is an error code, not a GPU
+ * fault.  What the check cannot see is memory freed by the caller while the
+ * call runs.  nrows == 0 returns KM_OK and does nothing.
+ * (Added within ABI 6: new entry points, no existing layout changes.) */
+#define KM_DT_F32 0
+#define KM_DT_F64 1
+#define KM_DT_F16 2
+#define KM_DT_BF16 3
+int km_load_device(km_ctx* ctx, int64_t row0, const void* dev_rows, int64_t nrows, int64_t src_stride_elems,
+                   int32_t dtype);
 /* Synthetic Gaussian blobs generated in HBM, keyed by global row (benchmarks). */
 int km_generate_blobs(km_ctx* ctx, int64_t n, int32_t d, int64_t global_row0, int32_t n_centers, float box,
                       float stddev, uint64_t seed);
@@ -286,6 +318,13 @@ int km_bernoulli_sample(km_ctx* ctx, const uint64_t* seeds, const int64_t* sizes
 int km_predict(km_ctx* ctx, int32_t* labels_out);
 /* Labels of the last km_assign_stats (device -> host). */
 int km_labels(km_ctx* ctx, int32_t* labels_out);
+/* km_labels with a device destination: n int32 copied device to device on the
+ * context's stream, then synchronised (km_predict(ctx, NULL) followed by this
+ * call leaves predictions in HBM with no host copy).  KM_ERR_STATE without
+ * data; KM_ERR_ARG for a null pointer with n > 0 and for a destination that is
+ * not device memory of the context's GPU (checked as in km_load_device).
+ * (Added within ABI 6.) */
+int km_labels_device(km_ctx* ctx, int32_t* dev_out);
 
 /* k-means|| seeding (Bahmani et al. 2012): an initialisation the reference
  * does not have (its only one is takeSample, kmeans_spark.py:58-82); the
